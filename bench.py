@@ -42,6 +42,7 @@ PROGRESSIVE_CALLS = 64         # --progressive
 READBACK_PASS = True
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
 COMM_TIMEOUT_S = 180.0         # the collective communicator bring-up may not hang the run
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: all arrays together
 
 
 def parse_args(argv=None):
@@ -66,13 +67,43 @@ def parse_args(argv=None):
     ap.add_argument("--no-readback-pass", action="store_true", help="--progressive without the second pass that reads the frame back after every call (kernel traces)")
     ap.add_argument("--no-extra-configs", action="store_true", help="the default run without the one-frame lines of cloud / sky / manylight")
     ap.add_argument("--detail-file", default=None, help="where the full record goes (default: bench_detail.json in the working directory); stdout carries the compact line only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed region, write the film of the last timed frame (what the caller of the timed "
+                                                                         "path receives) as DIR/<name>.npy, float32, at most %d MB in all" % (DUMP_LIMIT_BYTES >> 20))
     args = ap.parse_args(argv)
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
     args.extra_configs = args.config is None and not args.no_extra_configs and args.gpus == 1 and not args.spp and not args.spp_per_pass
     args.config = args.config or "cornell"
     global PROGRESSIVE_CALLS, READBACK_PASS
     PROGRESSIVE_CALLS = max(args.progressive, 0)
     READBACK_PASS = not args.no_readback_pass
     return args
+
+
+def dump_outputs(out_dir, acc, W, H, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the film accumulators of the last timed frame (rank 0's, after the reduce) as the timed path leaves them —
+    film_rgb_sum [H, W, 3] and film_weight_sum [H, W] — and image = rgb / weight (0 where no sample landed), all float32.  A film too
+    large for `limit` is written as a fixed, seeded sample of its pixels (sample_pixel_index: y * W + x).  -> {name: shape}"""
+    import numpy as np
+    n_px = W * H
+    acc = np.asarray(acc, dtype=np.float32)
+    rgb = acc[:3 * n_px].reshape(n_px, 3)
+    w = acc[3 * n_px:4 * n_px]
+    img = np.zeros_like(rgb)
+    np.divide(rgb, w[:, None], out=img, where=w[:, None] > 0)
+    shape = (H, W)
+    if n_px * 7 * 4 > limit:
+        keep = np.sort(np.random.default_rng(0).choice(n_px, limit // (7 * 4 + 8), replace=False))
+        rgb, w, img, shape = rgb[keep], w[keep], img[keep], (keep.size,)
+    else:
+        keep = None
+    arrays = {"film_rgb_sum": rgb.reshape(shape + (3,)), "film_weight_sum": w.reshape(shape), "image": img.reshape(shape + (3,))}
+    if keep is not None:
+        arrays["sample_pixel_index"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def launch_ranks(args):
@@ -813,6 +844,7 @@ def main():
         #      1e-2 relative L2.  Anything else ends the run with a non-zero exit code AFTER the line is printed.
         timed_acc = accum.detach().cpu().numpy().copy()
         n_px = W * H
+        dumped = dump_outputs(args.dump_outputs, timed_acc, W, H) if args.dump_outputs else None
         frame_check = {"finite": bool(np.isfinite(timed_acc).all() and (timed_acc[:3 * n_px] >= 0).all()),
                        "mean_weight_per_pixel": round(float(timed_acc[3 * n_px:].mean()), 4), "mean_rgb_sum": round(float(timed_acc[:3 * n_px].mean()), 6)}
         frame_check["ok"] = frame_check["finite"] and frame_check["mean_rgb_sum"] > 0
@@ -871,6 +903,8 @@ def main():
             "setup_seconds": round(setup_s, 3),
             "roofline": roofline, "rooflines": rooflines, "cpu_baseline": cpu, "frame_check": frame_check,
         }
+        if dumped is not None:
+            result["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped}
     if comm is not None:
         comm.close()
     if world > 1:

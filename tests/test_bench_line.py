@@ -9,6 +9,8 @@ import json
 import os
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -121,3 +123,43 @@ def test_utilisation_digests_carry_the_measured_valu_occupancy():
         for k, e in fams.items():
             assert 0.0 < e["valu_issue_frac"] <= e["valu_busy"] <= 1.0, (cfg, k, e)
             assert 0.0 < e["lane_util"] <= 1.0 and 0.5 < e["waves_per_simd"] <= 8.0, (cfg, k, e)
+
+
+def test_steps_is_the_timed_frame_count():
+    bench = _bench()
+    assert bench.parse_args(["--steps", "3"]).steps == 3
+    assert bench.parse_args([]).steps is None             # main() picks the config's default
+    for bad in ("0", "-2"):
+        with contextlib.redirect_stderr(io.StringIO()), pytest.raises(SystemExit):
+            bench.parse_args(["--steps", bad])
+
+
+def test_dump_outputs_writes_the_timed_film(tmp_path):
+    """--dump-outputs: the accumulators of the last timed frame ([rgb interleaved per pixel] then [weight per pixel]) as float32 arrays;
+    a film over the size limit is written as the same seeded pixel sample on every run"""
+    import numpy as np
+    bench = _bench()
+    W, H = 5, 3
+    rng = np.random.default_rng(1)
+    rgb = rng.random((H, W, 3)).astype(np.float32)
+    w = rng.integers(0, 4, (H, W)).astype(np.float32)
+    acc = np.concatenate([rgb.ravel(), w.ravel()])
+    shapes = bench.dump_outputs(str(tmp_path / "full"), acc, W, H)
+    assert shapes == {"film_rgb_sum": [H, W, 3], "film_weight_sum": [H, W], "image": [H, W, 3]}
+    got = {k: np.load(str(tmp_path / "full" / (k + ".npy"))) for k in shapes}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["film_rgb_sum"], rgb) and np.array_equal(got["film_weight_sum"], w)
+    want = np.where(w[..., None] > 0, rgb / np.maximum(w, 1)[..., None], 0)
+    assert np.allclose(got["image"], want, rtol=1e-6, atol=0)
+    limit = 7 * 4 * 6 + 8 * 6                               # room for 6 of the 15 pixels
+    for run in ("a", "b"):
+        shapes = bench.dump_outputs(str(tmp_path / run), acc, W, H, limit=limit)
+    assert shapes["film_rgb_sum"] == [6, 3] and shapes["sample_pixel_index"] == [6]
+    total = 0
+    for k in shapes:
+        a, b = (np.load(str(tmp_path / run / (k + ".npy"))) for run in ("a", "b"))
+        assert np.array_equal(a, b), k
+        total += a.nbytes
+    assert total <= limit
+    idx = np.load(str(tmp_path / "a" / "sample_pixel_index.npy")).astype(int)
+    assert np.array_equal(np.load(str(tmp_path / "a" / "film_rgb_sum.npy")), rgb.reshape(-1, 3)[idx])

@@ -31,24 +31,18 @@ def test_reference_data_tables_are_pinned():
 
 
 def test_reference_data_tables_match_the_reference_source():
-    """where the reference tree is present (the build container), the Sobol matrices and CIE tables are re-read from its sources"""
-    ref = "/root/reference/src"
-    if not os.path.isdir(ref):
-        pytest.skip("reference tree not present")
-    import re
-    import extract_reference_tables as ex
-    sob = ex.grab_block(open(os.path.join(ref, "sampler/sobol_matrices.jl")).read(), "SobolMatrices32")
-    arr = np.array([int(t, 16) for t in sob], dtype=np.uint32)
+    """the Sobol matrices and CIE tables the package ships are the ones parsed out of the reference's sources: reference_index.json
+    holds their digests (tests/golden/make_reference_index.py, run against the reference tree)"""
+    want = json.load(open(os.path.join(HERE, "reference_index.json")))["tables"]
     have = np.fromfile(os.path.join(ROOT, "hikari.jl_amd", "data", "sobol_matrices.bin"), dtype=np.uint32)
-    assert np.array_equal(arr, have)
-    col = open(os.path.join(ref, "spectral/color.jl")).read()
+    s = want["SobolMatrices32"]
+    assert have.size == s["count"] and hashlib.sha256(have.tobytes()).hexdigest() == s["sha256"]
     xyz = np.fromfile(os.path.join(ROOT, "hikari.jl_amd", "data", "cie_xyz.bin"), dtype=np.float32)
-    got = []
-    for nm in ("CIE_X", "CIE_Y", "CIE_Z"):
-        t = ex.grab_block(col, nm)
-        got.append(np.array([float(re.sub(r"f0$", "", x)) for x in t], dtype=np.float32))
-    got = np.concatenate(got)
-    assert got.size <= xyz.size and np.array_equal(got, xyz[-got.size:] if xyz.size != got.size else xyz)
+    n = [want[nm]["count"] for nm in ("CIE_X", "CIE_Y", "CIE_Z")]
+    assert sum(n) <= xyz.size
+    tail = xyz[xyz.size - sum(n):]
+    for nm, part in zip(("CIE_X", "CIE_Y", "CIE_Z"), np.split(tail, np.cumsum(n)[:-1])):
+        assert hashlib.sha256(part.tobytes()).hexdigest() == want[nm]["sha256"], nm
 
 
 @pytest.mark.parametrize("name", CASES)
