@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <map>
 #include <memory>
 #include <mutex>
 
@@ -56,6 +57,9 @@ void launch_test_mix(hipStream_t, const DScene&, int, int, const float*, const f
 void launch_test_medium(hipStream_t, const DScene&, const DTables&, int, int, int, const float*, const float*, const float*, const float*, float*);
 int test_majorant_stride();
 void launch_test_trace_lean(hipStream_t, int, const DScene&, int, int, const float*, const float*, const float*, float*, int*, float*);
+void launch_slot_of_prim(hipStream_t, const float4*, int, int*);
+void launch_xform_tris(hipStream_t, const DXform&, int, int, const float*, const float*, const float*, const int*, float*, float*, float*, float*, float4*);
+void launch_refit_level(hipStream_t, int, int, DNode*, DQNode*, const DQGrid&, const float4*, const float*);
 }  // namespace hk
 
 static thread_local std::string g_err;
@@ -317,7 +321,32 @@ struct hk_scene {
     int n_materials = 0;
     int bvh_nodes = 0, bvh_leaf_tris = 0, bvh_depth = 0;
     hk::LightBVH lbvh;
+    // ---- in-place edits (hk_scene_set_transform, hk_scene_update_materials) ----
+    std::vector<hk_material> h_materials;   // the records as created / last updated: what an update is checked against
+    int n_textures = 0, n_spectra = 0;
+    std::vector<int> level_start;           // breadth-first node levels: level L is [level_start[L], level_start[L + 1])
+    DevBuf base_pos, base_nrm, base_tan, slot_of_prim;   // geometry as created and the leaf slot of every triangle (first transform)
+    bool have_base = false;
+    bool qnodes_built = false;              // s->qnodes holds a quantised tree (D.qnodes is null while no grid is known to contain it)
+    enum { XF_BLOCK = 1024 };
+    std::vector<float> block_box;           // deep trees: lo[3] hi[3] of the base positions of every XF_BLOCK triangles
+    struct Xf {
+        int end;
+        bool identity;
+        float m[12];
+    };
+    std::map<int, Xf> xf;                   // transform of every triangle interval [key, end): the grid of the quantised nodes
+    struct Staging {                        // pinned upload buffers of material records, reused once their copy has run
+        void* host = nullptr;
+        size_t bytes = 0;
+        hipEvent_t ev = nullptr;
+    };
+    std::vector<Staging> staging;
     ~hk_scene() {
+        for (auto& st : staging) {
+            if (st.ev) (void)hipEventSynchronize(st.ev), (void)hipEventDestroy(st.ev);
+            if (st.host) (void)hipHostFree(st.host);
+        }
         for (auto* b : tex_data) delete b;
         for (auto* b : spec_data) delete b;
         for (auto* b : media_data) delete b;
@@ -581,6 +610,51 @@ int bake_mode(int kind, int slot) {
     if ((kind == HK_MAT_CONDUCTOR || kind == HK_MAT_COATED_CONDUCTOR) && slot < 2) return BAKE_UNBOUNDED;
     return BAKE_BOUNDED;
 }
+// The device record of a material: constant colours baked into sigmoid coefficients (hk_scene_create, hk_scene_update_materials).
+void bake_material(const hk::RGB2Spec& t, const hk_material& m, DMaterial& o) {
+    std::memset(&o, 0, sizeof o);
+    o.kind = (m.kind >= 0 && m.kind <= HK_MAT_FALLBACK) ? m.kind : HK_MAT_FALLBACK;
+    o.flags = m.flags;
+    std::memcpy(o.i, m.i, sizeof o.i);
+    std::memcpy(o.spectrum, m.spectrum, sizeof o.spectrum);
+    std::memcpy(o.mix_key, m.mix_key, sizeof o.mix_key);
+    for (int k = 0; k < 4; ++k) {
+        DSpectrumParam& sp = o.rgb[k];
+        sp.tex = m.rgb[k].tex;
+        std::memcpy(sp.rgba, m.rgb[k].c, 16);
+        float cf[4] = {0, 0, 0, 0};
+        if (sp.tex < 0) {
+            float r = m.rgb[k].c[0], g = m.rgb[k].c[1], b = m.rgb[k].c[2];
+            if (o.kind == HK_MAT_DIFFUSE_TRANSMISSION && k < 2) {  // clamp(rgb * scale, 0, 1) (spectral-eval.jl:2098-2103)
+                const float sc = m.f[0].v;
+                r = clampf(r * sc, 0.0f, 1.0f), g = clampf(g * sc, 0.0f, 1.0f), b = clampf(b * sc, 0.0f, 1.0f);
+            }
+            if (o.kind == HK_MAT_COATED_CONDUCTOR && k == 2)  // reflectance mode: clamp(r, 0, 0.9999) (:2924-2928)
+                r = clampf(r, 0.0f, 0.9999f), g = clampf(g, 0.0f, 0.9999f), b = clampf(b, 0.0f, 0.9999f);
+            switch (bake_mode(o.kind, k)) {
+                case BAKE_BOUNDED_CLAMP:
+                    r = clampf(r, 0.0f, INFINITY);
+                    g = clampf(g, 0.0f, INFINITY);
+                    b = clampf(b, 0.0f, INFINITY);
+                    bake_bounded(t, r, g, b, cf);
+                    break;
+                case BAKE_UNBOUNDED: bake_unbounded(t, r, g, b, cf); break;
+                default: bake_bounded(t, r, g, b, cf); break;
+            }
+        }
+        sp.coef = make_float4(cf[0], cf[1], cf[2], cf[3]);
+    }
+    for (int k = 0; k < 8; ++k) {
+        o.f[k] = m.f[k].v;
+        o.ftex[k] = m.f[k].tex;
+    }
+}
+void node_boxes(const hk::BVHNode& n, float lo[2][3], float hi[2][3]) {
+    for (int k = 0; k < 3; ++k) lo[0][k] = n.lo0[k], hi[0][k] = n.hi0[k], lo[1][k] = n.lo1[k], hi[1][k] = n.hi1[k];
+}
+// Alpha-tested surface (Matte with an alpha texture or alpha < 1).  This class decides DScene::all_opaque, the HK_TRI_OPAQUE bits and so
+// which kernel variants run: hk_scene_create classifies with it, and hk_scene_update_materials refuses a record whose class differs.
+bool material_alpha_tested(const hk_material& m) { return m.kind == HK_MAT_MATTE && (m.rgb[0].tex >= 0 || m.rgb[0].c[3] < 1.0f); }
 }  // namespace
 
 
@@ -655,10 +729,7 @@ extern "C" int32_t hk_scene_create(hk_ctx* c, const hk_scene_desc* d, hk_scene**
     const int T = d->n_triangles;
     // ---- classify surfaces: opaque = no medium transition and no alpha test possible ----
     std::vector<uint8_t> mat_alpha(d->n_materials > 0 ? d->n_materials : 1, 0);
-    for (int i = 0; i < d->n_materials; ++i) {
-        const hk_material& m = d->materials[i];
-        if (m.kind == HK_MAT_MATTE && (m.rgb[0].tex >= 0 || m.rgb[0].c[3] < 1.0f)) mat_alpha[i] = 1;
-    }
+    for (int i = 0; i < d->n_materials; ++i) mat_alpha[i] = material_alpha_tested(d->materials[i]) ? 1 : 0;
     bool all_opaque = true;
     std::vector<uint8_t> mi_opaque(d->n_media_interfaces > 0 ? d->n_media_interfaces : 1, 1);
     for (int i = 0; i < d->n_media_interfaces; ++i) {
@@ -683,9 +754,9 @@ extern "C" int32_t hk_scene_create(hk_ctx* c, const hk_scene_desc* d, hk_scene**
     std::vector<DNode> dn(bvh.nodes.size() ? bvh.nodes.size() : 1);
     for (size_t i = 0; i < bvh.nodes.size(); ++i) {
         const hk::BVHNode& n = bvh.nodes[i];
-        dn[i].a = make_float4(n.lo0[0], n.hi0[0], n.lo0[1], n.hi0[1]);
-        dn[i].b = make_float4(n.lo0[2], n.hi0[2], n.lo1[0], n.hi1[0]);
-        dn[i].c = make_float4(n.lo1[1], n.hi1[1], n.lo1[2], n.hi1[2]);
+        float lo[2][3], hi[2][3];
+        node_boxes(n, lo, hi);
+        hk_pack_node_boxes(dn[i], lo, hi);
         dn[i].c0 = n.c0;
         dn[i].c1 = n.c1;
         dn[i].pad0 = dn[i].pad1 = 0;
@@ -703,9 +774,7 @@ extern "C" int32_t hk_scene_create(hk_ctx* c, const hk_scene_desc* d, hk_scene**
         float pw, fw;
         std::memcpy(&pw, &prim, 4);
         std::memcpy(&fw, &flags, 4);
-        lt[3 * i + 0] = make_float4(p[0], p[1], p[2], pw);
-        lt[3 * i + 1] = make_float4(p[3] - p[0], p[4] - p[1], p[5] - p[2], fw);  // e1 = v1 - v0
-        lt[3 * i + 2] = make_float4(p[6] - p[0], p[7] - p[1], p[8] - p[2], 0.0f);  // e2 = v2 - v0
+        hk_pack_leaf_tri(&lt[3 * i], p, pw, fw, 0.0f);
     }
     HIP_TRY(s->nodes.upload(dn.data(), dn.size() * sizeof(DNode)));
     // ---- quantised copy of a deep tree (DQNode, hk_types.h): 16-bit planes on a grid over the root box, lo rounded down and hi rounded
@@ -723,22 +792,19 @@ extern "C" int32_t hk_scene_create(hk_ctx* c, const hk_scene_desc* d, hk_scene**
                 q_base[k] = (float)((double)bvh.lo[k] - 3.0 * (double)q_cell[k]);
             }
             std::vector<DQNode> qn(bvh.nodes.size());
-            auto quant = [&](float v, int axis, bool upper) -> uint32_t {
-                if (!std::isfinite(v)) return upper ? 0u : 65535u;   // an empty box stays empty (lo > hi)
-                const double g = ((double)v - (double)q_base[axis]) / (double)q_cell[axis];
-                const double q = upper ? std::ceil(g) + 1.0 : std::floor(g) - 1.0;
-                return (uint32_t)std::min(std::max(q, 0.0), 65535.0);
-            };
             bool ok = true;
             for (size_t i = 0; i < bvh.nodes.size(); ++i) {
                 const hk::BVHNode& n = bvh.nodes[i];
+                float lo[2][3], hi[2][3];
+                node_boxes(n, lo, hi);
+                hk_quant_node(qn[i], lo, hi, q_base, q_cell);   // (an empty box stays empty: lo > hi)
                 for (int c = 0; c < 2; ++c)
                     for (int k = 0; k < 3; ++k) {
-                        const float lo = c ? n.lo1[k] : n.lo0[k], hi = c ? n.hi1[k] : n.hi0[k];
-                        const uint32_t ql = quant(lo, k, false), qh = quant(hi, k, true);
+                        const uint32_t ql = qn[i].w[3 * c + k] & 0xffffu, qh = qn[i].w[3 * c + k] >> 16;
                         // the grid must contain the box with its margin (a box outside the root's bounds would be clipped: never for a child of the root)
-                        if (std::isfinite(lo) && std::isfinite(hi) && ((double)q_base[k] + ql * (double)q_cell[k] > lo || (double)q_base[k] + qh * (double)q_cell[k] < hi)) ok = false;
-                        qn[i].w[3 * c + k] = ql | (qh << 16);
+                        if (std::isfinite(lo[c][k]) && std::isfinite(hi[c][k]) &&
+                            ((double)q_base[k] + ql * (double)q_cell[k] > lo[c][k] || (double)q_base[k] + qh * (double)q_cell[k] < hi[c][k]))
+                            ok = false;
                     }
                 qn[i].c0 = n.c0;
                 qn[i].c1 = n.c1;
@@ -807,44 +873,8 @@ extern "C" int32_t hk_scene_create(hk_ctx* c, const hk_scene_desc* d, hk_scene**
     std::vector<DMaterial> dm(d->n_materials > 0 ? d->n_materials : 1);
     std::memset(dm.data(), 0, dm.size() * sizeof(DMaterial));
     for (int i = 0; i < d->n_materials; ++i) {
-        const hk_material& m = d->materials[i];
-        DMaterial& o = dm[i];
-        o.kind = (m.kind >= 0 && m.kind <= HK_MAT_FALLBACK) ? m.kind : HK_MAT_FALLBACK;
-        o.flags = m.flags;
-        std::memcpy(o.i, m.i, sizeof o.i);
-        std::memcpy(o.spectrum, m.spectrum, sizeof o.spectrum);
-        std::memcpy(o.mix_key, m.mix_key, sizeof o.mix_key);
-        for (int k = 0; k < 4; ++k) {
-            DSpectrumParam& sp = o.rgb[k];
-            sp.tex = m.rgb[k].tex;
-            std::memcpy(sp.rgba, m.rgb[k].c, 16);
-            float cf[4] = {0, 0, 0, 0};
-            if (sp.tex < 0) {
-                float r = m.rgb[k].c[0], g = m.rgb[k].c[1], b = m.rgb[k].c[2];
-                if (o.kind == HK_MAT_DIFFUSE_TRANSMISSION && k < 2) {  // clamp(rgb * scale, 0, 1) (spectral-eval.jl:2098-2103)
-                    const float sc = m.f[0].v;
-                    r = clampf(r * sc, 0.0f, 1.0f), g = clampf(g * sc, 0.0f, 1.0f), b = clampf(b * sc, 0.0f, 1.0f);
-                }
-                if (o.kind == HK_MAT_COATED_CONDUCTOR && k == 2)  // reflectance mode: clamp(r, 0, 0.9999) (:2924-2928)
-                    r = clampf(r, 0.0f, 0.9999f), g = clampf(g, 0.0f, 0.9999f), b = clampf(b, 0.0f, 0.9999f);
-                switch (bake_mode(o.kind, k)) {
-                    case BAKE_BOUNDED_CLAMP:
-                        r = clampf(r, 0.0f, INFINITY);
-                        g = clampf(g, 0.0f, INFINITY);
-                        b = clampf(b, 0.0f, INFINITY);
-                        bake_bounded(c->r2s_host, r, g, b, cf);
-                        break;
-                    case BAKE_UNBOUNDED: bake_unbounded(c->r2s_host, r, g, b, cf); break;
-                    default: bake_bounded(c->r2s_host, r, g, b, cf); break;
-                }
-            }
-            sp.coef = make_float4(cf[0], cf[1], cf[2], cf[3]);
-        }
-        for (int k = 0; k < 8; ++k) {
-            o.f[k] = m.f[k].v;
-            o.ftex[k] = m.f[k].tex;
-        }
-        if (o.kind != HK_MAT_MIX) s->kinds_mask |= 1u << o.kind;
+        bake_material(c->r2s_host, d->materials[i], dm[i]);
+        if (dm[i].kind != HK_MAT_MIX) s->kinds_mask |= 1u << dm[i].kind;
     }
     s->n_materials = d->n_materials;
     HIP_TRY(s->materials.upload(dm.data(), dm.size() * sizeof(DMaterial)));
@@ -1237,6 +1267,36 @@ extern "C" int32_t hk_scene_create(hk_ctx* c, const hk_scene_desc* d, hk_scene**
     D.simple_lights = (!has_escape && !textured_emitters && d->n_textures == 0) ? 1 : 0;
     D.all_opaque = all_opaque ? 1 : 0;
     D.bvh_depth = bvh.max_depth;
+    // what the in-place edits need: the material records, the node levels, the base bounds per triangle block of a quantised tree
+    s->h_materials.assign(d->materials, d->materials + d->n_materials);
+    s->n_textures = d->n_textures;
+    s->n_spectra = d->n_spectra;
+    if (!bvh.nodes.empty()) {   // breadth-first order: a level is a contiguous range (bvh_build.cpp)
+        std::vector<int> depth(bvh.nodes.size(), 0);
+        s->level_start.push_back(0);
+        for (size_t i = 0; i < bvh.nodes.size(); ++i) {
+            if (bvh.nodes[i].c0 >= 0) depth[bvh.nodes[i].c0] = depth[i] + 1;
+            if (bvh.nodes[i].c1 >= 0) depth[bvh.nodes[i].c1] = depth[i] + 1;
+            if (i > 0 && depth[i] != depth[i - 1]) s->level_start.push_back((int)i);
+        }
+        s->level_start.push_back((int)bvh.nodes.size());
+    }
+    s->qnodes_built = have_qnodes;
+    if (have_qnodes) {
+        const int nb = (T + hk_scene::XF_BLOCK - 1) / hk_scene::XF_BLOCK;
+        s->block_box.resize(6 * (size_t)nb);
+        for (int b = 0; b < nb; ++b) {
+            float* bb = s->block_box.data() + 6 * (size_t)b;
+            for (int k = 0; k < 3; ++k) bb[k] = INFINITY, bb[3 + k] = -INFINITY;
+            for (int t = b * hk_scene::XF_BLOCK; t < std::min(T, (b + 1) * hk_scene::XF_BLOCK); ++t)
+                for (int v = 0; v < 9; ++v) {
+                    const float x = d->positions[9 * (size_t)t + v];
+                    bb[v % 3] = std::min(bb[v % 3], x);
+                    bb[3 + v % 3] = std::max(bb[3 + v % 3], x);
+                }
+        }
+    }
+    if (T > 0) s->xf[0] = hk_scene::Xf{T, true, {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}};
     *out = guard.release();
     return HK_OK;
 }
@@ -1277,6 +1337,209 @@ extern "C" int32_t hk_scene_light_bvh_copy(hk_scene* s, int32_t* n_nodes, float*
         }
     if (bit_trails)
         for (size_t i = 0; i < s->lbvh.bit_trails.size(); ++i) bit_trails[i] = s->lbvh.bit_trails[i];
+    return HK_OK;
+}
+
+// ---- in-place scene edits -----------------------------------------------------------------------------------------------------
+// Neither entry point waits for the device: the noted calls are rendered first (against the scene as it was), the lanes are joined, and
+// the work is enqueued on the context's stream behind everything already there.  Every argument is checked before anything changes.
+// Caches keyed by the scene that an edit must not invalidate, and why it does not: DScene::all_opaque and the HK_TRI_OPAQUE bits (opacity
+// class of every material and the medium interfaces are unchanged), kinds_mask (kinds unchanged), simple_lights / has_escape_lights
+// (lights and textures unchanged), bvh_depth and n_nodes (topology unchanged), the light BVH (built from the base geometry, Q18),
+// the context's noted call (flushed) and lanes (joined); the integrator's path state is sized from those flags only.
+namespace {
+// the transform of the header's arithmetic: m as given, its normal matrix in double, identity => copy
+std::string make_xform(const float* m34, DXform& X) {
+    for (int j = 0; j < 12; ++j)
+        if (!std::isfinite(m34[j])) return "hk_scene_set_transform: non-finite matrix entry";
+    std::memcpy(X.m, m34, sizeof X.m);
+    static const float id[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    X.copy = 1;
+    for (int j = 0; j < 12; ++j)
+        if (m34[j] != id[j]) X.copy = 0;
+    double A[3][3], Cf[3][3];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) A[i][j] = m34[4 * i + j];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+            Cf[i][j] = A[i1][j1] * A[i2][j2] - A[i1][j2] * A[i2][j1];
+        }
+    const double det = (A[0][0] * Cf[0][0] + A[0][1] * Cf[0][1]) + A[0][2] * Cf[0][2];
+    if (!(det != 0.0) || !std::isfinite(det)) return "hk_scene_set_transform: singular matrix";
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            X.nm[3 * i + j] = (float)(Cf[i][j] / det);
+            if (!std::isfinite(X.nm[3 * i + j])) return "hk_scene_set_transform: the normal matrix overflows";
+        }
+    return std::string();
+}
+// A grid for the quantised nodes that contains every node after the edit, without reading the device: the union over the transform
+// intervals of (identity) the base bounds of their triangle blocks, (otherwise) the 8 corners of that box through the point formula in
+// double, widened by a bound on the binary32 rounding; then one cell of margin.  false: no finite grid (the float nodes are used).
+bool quant_grid(const hk_scene* s, DQGrid& g) {
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    const int B = hk_scene::XF_BLOCK;
+    for (const auto& kv : s->xf) {
+        const int a = kv.first, e = kv.second.end;
+        double blo[3] = {INFINITY, INFINITY, INFINITY}, bhi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (int b = a / B; b <= (e - 1) / B; ++b)   // whole blocks: a superset of the interval
+            for (int k = 0; k < 3; ++k) blo[k] = std::min(blo[k], (double)s->block_box[6 * (size_t)b + k]), bhi[k] = std::max(bhi[k], (double)s->block_box[6 * (size_t)b + 3 + k]);
+        if (kv.second.identity) {
+            for (int k = 0; k < 3; ++k) lo[k] = std::min(lo[k], blo[k]), hi[k] = std::max(hi[k], bhi[k]);
+            continue;
+        }
+        const float* m = kv.second.m;
+        for (int k = 0; k < 3; ++k) {
+            double mag = std::fabs((double)m[4 * k + 3]);
+            for (int j = 0; j < 3; ++j) mag += std::fabs((double)m[4 * k + j]) * std::max(std::fabs(blo[j]), std::fabs(bhi[j]));
+            const double err = mag * std::ldexp(1.0, -20);   // >= the rounding of three products and three sums in binary32
+            for (int corner = 0; corner < 8; ++corner) {
+                double v = m[4 * k + 3];
+                for (int j = 0; j < 3; ++j) v += (double)m[4 * k + j] * ((corner >> j) & 1 ? bhi[j] : blo[j]);
+                lo[k] = std::min(lo[k], v - err), hi[k] = std::max(hi[k], v + err);
+            }
+        }
+    }
+    for (int k = 0; k < 3; ++k) {
+        const double cell = (hi[k] - lo[k]) / 65527.0;
+        if (!std::isfinite(lo[k]) || !std::isfinite(hi[k]) || !std::isfinite(cell)) return false;
+        const double l = lo[k] - cell, h = hi[k] + cell;   // one cell of margin; then the grid as hk_scene_create lays it over a box
+        g.cell[k] = (float)std::max((h - l) / 65527.0, 1e-30);
+        g.base[k] = (float)(l - 3.0 * (double)g.cell[k]);
+        if (!std::isfinite(g.base[k]) || !std::isfinite(g.cell[k])) return false;
+    }
+    return true;
+}
+}  // namespace
+
+extern "C" int32_t hk_scene_set_transform(hk_scene* s, int32_t first_tri, int32_t n_tris, const float* m34) {
+    if (!s || !m34) return fail(HK_ERR_INVALID, "hk_scene_set_transform: null argument");
+    const int T = s->d.n_tris;
+    if (T <= 0) return fail(HK_ERR_INVALID, "hk_scene_set_transform: the scene has no triangles");
+    if (first_tri < 0 || n_tris < 1 || (int64_t)first_tri + n_tris > T) return fail(HK_ERR_INVALID, "hk_scene_set_transform: triangle range outside the scene");
+    DXform X{};
+    {
+        std::string bad = make_xform(m34, X);
+        if (!bad.empty()) return fail(HK_ERR_INVALID, bad);
+    }
+    hk_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    KnobScope knobs(&c->knobs);
+    if (int e = join_lanes(c)) return e;   // noted calls render the scene as it was; the lanes finish before the stream rewrites it
+    DScene& D = s->d;
+    if (!s->have_base) {   // the arrays as created, and the leaf slot of every triangle (first edit only: an unedited scene pays nothing)
+        HIP_TRY(s->base_pos.alloc((size_t)T * 36));
+        HIP_TRY(hipMemcpyAsync(s->base_pos.p, D.positions, (size_t)T * 36, hipMemcpyDeviceToDevice, c->stream));
+        if (D.normals) {
+            HIP_TRY(s->base_nrm.alloc((size_t)T * 36));
+            HIP_TRY(hipMemcpyAsync(s->base_nrm.p, D.normals, (size_t)T * 36, hipMemcpyDeviceToDevice, c->stream));
+        }
+        if (D.tangents) {
+            HIP_TRY(s->base_tan.alloc((size_t)T * 36));
+            HIP_TRY(hipMemcpyAsync(s->base_tan.p, D.tangents, (size_t)T * 36, hipMemcpyDeviceToDevice, c->stream));
+        }
+        HIP_TRY(s->slot_of_prim.alloc((size_t)T * 4));
+        hk::launch_slot_of_prim(c->stream, D.leaf_tris, s->bvh_leaf_tris, s->slot_of_prim.as<int>());
+        HIP_TRY(hipGetLastError());
+        s->have_base = true;
+    }
+    hk::launch_xform_tris(c->stream, X, first_tri, n_tris, s->base_pos.as<float>(), D.normals ? s->base_nrm.as<float>() : nullptr, D.tangents ? s->base_tan.as<float>() : nullptr,
+                          s->slot_of_prim.as<int>(), s->positions.as<float>(), D.normals ? s->normals.as<float>() : nullptr, D.tangents ? s->tangents.as<float>() : nullptr,
+                          D.tri_shade ? s->tri_shade.as<float>() : nullptr, s->leaf_tris.as<float4>());
+    HIP_TRY(hipGetLastError());
+    {   // the transform of every triangle interval (the quantised grid's bookkeeping)
+        const int a = first_tri, e = first_tri + n_tris;
+        auto split = [&](int at) {
+            if (at >= T) return;
+            auto it = std::prev(s->xf.upper_bound(at));
+            if (it->first == at) return;
+            hk_scene::Xf right = it->second;
+            it->second.end = at;
+            s->xf[at] = right;
+        };
+        split(a);
+        split(e);
+        s->xf.erase(s->xf.lower_bound(a), s->xf.lower_bound(e));
+        hk_scene::Xf x{e, X.copy != 0, {}};
+        std::memcpy(x.m, m34, sizeof x.m);
+        s->xf[a] = x;
+    }
+    DQGrid grid{};
+    DQNode* qn = nullptr;
+    if (s->qnodes_built) {
+        if (quant_grid(s, grid)) {
+            qn = s->qnodes.as<DQNode>();
+            for (int k = 0; k < 3; ++k) D.q_base[k] = grid.base[k], D.q_cell[k] = grid.cell[k];
+        }
+        D.qnodes = qn;   // null: no grid is known to hold the moved tree, the traversal reads the float nodes (same hits)
+    }
+    for (int L = (int)s->level_start.size() - 2; L >= 0; --L) {   // deepest level first; nothing to do when the root is a leaf
+        hk::launch_refit_level(c->stream, s->level_start[L], s->level_start[L + 1], s->nodes.as<DNode>(), qn, grid, D.leaf_tris, D.positions);
+        HIP_TRY(hipGetLastError());
+    }
+    return HK_OK;
+}
+
+namespace {
+// what an update may change: everything but the kind, a Mix's children, and the opacity class; indices must stay in range
+std::string check_material_update(const hk_scene* s, int idx, const hk_material& old, const hk_material& m) {
+    const std::string at = "hk_scene_update_materials: material " + std::to_string(idx) + ": ";
+    if (m.kind != old.kind) return at + "the kind differs from the record it replaces";
+    if (m.kind == HK_MAT_MIX && (m.i[0] != old.i[0] || m.i[1] != old.i[1] || std::memcmp(m.mix_key, old.mix_key, sizeof m.mix_key) != 0))
+        return at + "a MixMaterial's children (i[], mix_key) cannot change";
+    for (int k = 0; k < 4; ++k)
+        if (m.rgb[k].tex >= s->n_textures) return at + "rgb texture index out of range";
+    for (int k = 0; k < 8; ++k)
+        if (m.f[k].tex >= s->n_textures) return at + "float texture index out of range";
+    if (m.kind == HK_MAT_CONDUCTOR || m.kind == HK_MAT_COATED_CONDUCTOR)
+        for (int k = 0; k < 2; ++k)
+            if (m.spectrum[k] >= s->n_spectra) return at + "spectrum index out of range";
+    if (material_alpha_tested(m) != material_alpha_tested(old)) return at + "the opacity class (Matte alpha texture / alpha < 1) cannot change";
+    return std::string();
+}
+}  // namespace
+
+extern "C" int32_t hk_scene_update_materials(hk_scene* s, int32_t first, int32_t n, const hk_material* materials) {
+    if (!s || !materials) return fail(HK_ERR_INVALID, "hk_scene_update_materials: null argument");
+    if (first < 0 || n < 1 || (int64_t)first + n > s->n_materials) return fail(HK_ERR_INVALID, "hk_scene_update_materials: material range outside the scene");
+    for (int j = 0; j < n; ++j) {
+        std::string bad = check_material_update(s, first + j, s->h_materials[first + j], materials[j]);
+        if (!bad.empty()) return fail(HK_ERR_INVALID, bad);
+    }
+    hk_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    KnobScope knobs(&c->knobs);
+    const size_t bytes = (size_t)n * sizeof(DMaterial);
+    // a pinned staging buffer whose previous copy has run (at most four; the oldest is waited for only when all four are in flight)
+    hk_scene::Staging* st = nullptr;
+    for (auto& b : s->staging)
+        if (b.bytes >= bytes && hipEventQuery(b.ev) == hipSuccess) {
+            st = &b;
+            break;
+        }
+    if (!st) {
+        if (s->staging.size() < 4) {
+            s->staging.emplace_back();
+            st = &s->staging.back();
+            HIP_TRY(hipEventCreateWithFlags(&st->ev, hipEventDisableTiming));
+        } else {
+            st = &s->staging.front();
+            HIP_TRY(hipEventSynchronize(st->ev));
+        }
+        if (st->bytes < bytes) {
+            if (st->host) HIP_TRY(hipHostFree(st->host));
+            st->host = nullptr, st->bytes = 0;
+            HIP_TRY(hipHostMalloc(&st->host, bytes, hipHostMallocDefault));
+            st->bytes = bytes;
+        }
+    }
+    if (int e = join_lanes(c)) return e;   // noted calls render the old materials; the lanes finish before the stream rewrites them
+    DMaterial* rec = static_cast<DMaterial*>(st->host);
+    for (int j = 0; j < n; ++j) bake_material(c->r2s_host, materials[j], rec[j]);
+    HIP_TRY(hipMemcpyAsync(s->materials.as<DMaterial>() + first, rec, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipEventRecord(st->ev, c->stream));
+    for (int j = 0; j < n; ++j) s->h_materials[first + j] = materials[j];
     return HK_OK;
 }
 

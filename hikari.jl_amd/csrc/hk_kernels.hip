@@ -4943,6 +4943,104 @@ __global__ void __launch_bounds__(256) k_denoise_atrous(hk_denoise_params P, int
 }
 
 // ---------------------------------------------------------------------------------------------------
+// SCENE EDITS (hk_scene_set_transform).  k_xform_tris rewrites the geometry of a triangle range from the base copies (the arrays as
+// created), k_refit_level recomputes the child boxes of one breadth-first level of the unchanged topology — launched deepest level first,
+// so the kernel boundary makes the level below visible to every CU.  Binary32 without contraction, the order of the header.
+// ---------------------------------------------------------------------------------------------------
+__global__ void k_slot_of_prim(const float4* __restrict__ leaf_tris, int n, int* __restrict__ slot_of_prim) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) slot_of_prim[__float_as_int(leaf_tris[3 * (size_t)i].w)] = i;
+}
+
+// n' = (N[k][0]*x + N[k][1]*y) + N[k][2]*z, then n' / sqrt((x*x + y*y) + z*z); a NaN vector (no normal) is copied
+__device__ inline void xform_dir(const float* M, int stride, const float* in, float* out) {
+    const float x = in[0], y = in[1], z = in[2];
+    if (x != x || y != y || z != z) {
+        out[0] = x, out[1] = y, out[2] = z;
+        return;
+    }
+    float r[3];
+    for (int k = 0; k < 3; ++k) r[k] = (M[stride * k] * x + M[stride * k + 1] * y) + M[stride * k + 2] * z;
+    const float len = sqrtf((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]);
+    for (int k = 0; k < 3; ++k) out[k] = r[k] / len;
+}
+
+__global__ void __launch_bounds__(256) k_xform_tris(DXform X, int first, int n, const float* __restrict__ bp, const float* __restrict__ bn, const float* __restrict__ bt,
+                                                    const int* __restrict__ slot_of_prim, float* __restrict__ pos, float* __restrict__ nrm, float* __restrict__ tan,
+                                                    float* __restrict__ shade, float4* __restrict__ leaf) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const size_t t = (size_t)first + i;
+        float p[9];
+        for (int v = 0; v < 3; ++v) {
+            const float x = bp[9 * t + 3 * v], y = bp[9 * t + 3 * v + 1], z = bp[9 * t + 3 * v + 2];
+            for (int k = 0; k < 3; ++k)
+                p[3 * v + k] = X.copy ? bp[9 * t + 3 * v + k] : ((X.m[4 * k] * x + X.m[4 * k + 1] * y) + X.m[4 * k + 2] * z) + X.m[4 * k + 3];
+        }
+        for (int j = 0; j < 9; ++j) pos[9 * t + j] = p[j];
+        if (shade)
+            for (int j = 0; j < 9; ++j) shade[32 * t + j] = p[j];
+        if (nrm) {
+            float q[9];
+            for (int v = 0; v < 3; ++v) {
+                if (X.copy)
+                    for (int k = 0; k < 3; ++k) q[3 * v + k] = bn[9 * t + 3 * v + k];
+                else
+                    xform_dir(X.nm, 3, bn + 9 * t + 3 * v, q + 3 * v);
+            }
+            for (int j = 0; j < 9; ++j) nrm[9 * t + j] = q[j];
+            if (shade)
+                for (int j = 0; j < 9; ++j) shade[32 * t + 9 + j] = q[j];
+        }
+        if (tan) {
+            for (int v = 0; v < 3; ++v) {
+                float q[3];
+                if (X.copy)
+                    for (int k = 0; k < 3; ++k) q[k] = bt[9 * t + 3 * v + k];
+                else
+                    xform_dir(X.m, 4, bt + 9 * t + 3 * v, q);
+                for (int k = 0; k < 3; ++k) tan[9 * t + 3 * v + k] = q[k];
+            }
+        }
+        float4* L = leaf + 3 * (size_t)slot_of_prim[t];
+        hk_pack_leaf_tri(L, p, L[0].w, L[1].w, L[2].w);
+    }
+}
+
+// min / max as the builder's Box::grow (std::min / std::max)
+__device__ inline float grow_lo(float lo, float v) { return v < lo ? v : lo; }
+__device__ inline float grow_hi(float hi, float v) { return hi < v ? v : hi; }
+
+__global__ void __launch_bounds__(256) k_refit_level(int begin, int end, DNode* __restrict__ nodes, DQNode* __restrict__ qnodes, DQGrid grid,
+                                                     const float4* __restrict__ leaf, const float* __restrict__ pos) {
+    for (int i = begin + blockIdx.x * blockDim.x + threadIdx.x; i < end; i += gridDim.x * blockDim.x) {
+        DNode nd = nodes[i];
+        float lo[2][3], hi[2][3];
+        for (int c = 0; c < 2; ++c) {
+            const int ref = c ? nd.c1 : nd.c0;
+            for (int k = 0; k < 3; ++k) lo[c][k] = INFINITY, hi[c][k] = -INFINITY;
+            if (ref >= 0) {   // inner child: the union of its two boxes (written by the previous launch)
+                float cl[2][3], ch[2][3];
+                hk_unpack_node_boxes(nodes[ref], cl, ch);
+                for (int s = 0; s < 2; ++s)
+                    for (int k = 0; k < 3; ++k) lo[c][k] = grow_lo(lo[c][k], cl[s][k]), hi[c][k] = grow_hi(hi[c][k], ch[s][k]);
+            } else {          // leaf child: its triangles' world vertices, by prim
+                const int first = (~ref) >> 3, count = ((~ref) & 7) + 1;
+                for (int j = 0; j < count; ++j) {
+                    const float* p = pos + 9 * (size_t)__float_as_int(leaf[3 * (size_t)(first + j)].w);
+                    for (int v = 0; v < 9; ++v) lo[c][v % 3] = grow_lo(lo[c][v % 3], p[v]), hi[c][v % 3] = grow_hi(hi[c][v % 3], p[v]);
+                }
+            }
+        }
+        hk_pack_node_boxes(nd, lo, hi);
+        nodes[i].a = nd.a, nodes[i].b = nd.b, nodes[i].c = nd.c;
+        if (qnodes) {
+            DQNode q = qnodes[i];
+            hk_quant_node(q, lo, hi, grid.base, grid.cell);
+            for (int w = 0; w < 6; ++w) qnodes[i].w[w] = q.w[w];
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
 // launch wrappers (called from hk_api.cpp)
 // ---------------------------------------------------------------------------------------------------
 namespace hk {
@@ -5556,6 +5654,16 @@ void launch_denoise_variance(hipStream_t s, const float* src, float* variance, i
 void launch_denoise_atrous(hipStream_t s, const hk_denoise_params& P, int step, const float* src, const float* normal, const float* depth, const float* variance,
                            float* dst, int h, int w) {
     hipLaunchKernelGGL(k_denoise_atrous, dim3(grid_for(h * w, 256, 8192)), dim3(256), 0, s, P, step, src, normal, depth, variance, dst, h, w);
+}
+void launch_slot_of_prim(hipStream_t s, const float4* leaf, int n, int* slot_of_prim) {
+    hipLaunchKernelGGL(k_slot_of_prim, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, leaf, n, slot_of_prim);
+}
+void launch_xform_tris(hipStream_t s, const DXform& X, int first, int n, const float* bp, const float* bn, const float* bt, const int* slot_of_prim, float* pos, float* nrm,
+                       float* tan, float* shade, float4* leaf) {
+    hipLaunchKernelGGL(k_xform_tris, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, X, first, n, bp, bn, bt, slot_of_prim, pos, nrm, tan, shade, leaf);
+}
+void launch_refit_level(hipStream_t s, int begin, int end, DNode* nodes, DQNode* qnodes, const DQGrid& grid, const float4* leaf, const float* pos) {
+    hipLaunchKernelGGL(k_refit_level, dim3(grid_for(end - begin, 256, 8192)), dim3(256), 0, s, begin, end, nodes, qnodes, grid, leaf, pos);
 }
 void launch_aux(hipStream_t s, const DScene& sc, const DCamera& cam, int h, int w, float miss_depth, float* albedo, float* normal, float* depth) {
     hipLaunchKernelGGL(k_aux, dim3(grid_for(h * w, HK_TRACE_BLOCK, 2048)), dim3(HK_TRACE_BLOCK), 0, s, sc, cam, h, w, miss_depth, albedo, normal, depth);

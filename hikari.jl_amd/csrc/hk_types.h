@@ -157,6 +157,49 @@ struct DQNode {
     int c0, c1;
 };
 
+// RECORD PACKING shared by the host build (hk_scene_create) and the device refit (hk_scene_set_transform): one definition of each layout.
+// Child boxes of a DNode: lo[c][k], hi[c][k] for child c, axis k.
+__host__ __device__ inline void hk_pack_node_boxes(DNode& n, const float lo[2][3], const float hi[2][3]) {
+    n.a = make_float4(lo[0][0], hi[0][0], lo[0][1], hi[0][1]);
+    n.b = make_float4(lo[0][2], hi[0][2], lo[1][0], hi[1][0]);
+    n.c = make_float4(lo[1][1], hi[1][1], lo[1][2], hi[1][2]);
+}
+__host__ __device__ inline void hk_unpack_node_boxes(const DNode& n, float lo[2][3], float hi[2][3]) {
+    lo[0][0] = n.a.x, hi[0][0] = n.a.y, lo[0][1] = n.a.z, hi[0][1] = n.a.w;
+    lo[0][2] = n.b.x, hi[0][2] = n.b.y, lo[1][0] = n.b.z, hi[1][0] = n.b.w;
+    lo[1][1] = n.c.x, hi[1][1] = n.c.y, lo[1][2] = n.c.z, hi[1][2] = n.c.w;
+}
+// Leaf-triangle record from the world vertices p[9]: v0 | w0, e1 = v1 - v0 | w1, e2 = v2 - v0 | w2.
+__host__ __device__ inline void hk_pack_leaf_tri(float4* o, const float* p, float w0, float w1, float w2) {
+    o[0] = make_float4(p[0], p[1], p[2], w0);
+    o[1] = make_float4(p[3] - p[0], p[4] - p[1], p[5] - p[2], w1);
+    o[2] = make_float4(p[6] - p[0], p[7] - p[1], p[8] - p[2], w2);
+}
+// One box plane on the DQNode grid (plane = base + q * cell): lo rounded down and hi rounded up, one more cell of margin, clamped to
+// 16 bits; a non-finite plane (empty box) maps to lo > hi.  Evaluated in double on host and device alike.
+__host__ __device__ inline uint32_t hk_quant_plane(float v, float base, float cell, bool upper) {
+    if (!__builtin_isfinite(v)) return upper ? 0u : 65535u;
+    const double g = ((double)v - (double)base) / (double)cell;
+    const double q = upper ? ceil(g) + 1.0 : floor(g) - 1.0;
+    return (uint32_t)(q < 0.0 ? 0.0 : (q > 65535.0 ? 65535.0 : q));
+}
+__host__ __device__ inline void hk_quant_node(DQNode& q, const float lo[2][3], const float hi[2][3], const float base[3], const float cell[3]) {
+    for (int c = 0; c < 2; ++c)
+        for (int k = 0; k < 3; ++k) q.w[3 * c + k] = hk_quant_plane(lo[c][k], base[k], cell[k], false) | (hk_quant_plane(hi[c][k], base[k], cell[k], true) << 16);
+}
+
+// hk_scene_set_transform: m = 3x4 row-major affine applied to points, nm = its normal matrix (inverse transpose of the linear part,
+// computed on the host in double, rounded to binary32); copy = m is exactly the identity: the base arrays are copied back bit for bit.
+struct DXform {
+    float m[12];
+    float nm[9];
+    int copy;
+};
+// The grid of the quantised nodes (plane = base + q * cell).
+struct DQGrid {
+    float base[3], cell[3];
+};
+
 struct DScene {
     const DNode* nodes;
     const DQNode* qnodes;       // null unless the tree is deeper than 16 levels (and HK_QNODES != 0)

@@ -13,6 +13,40 @@ from . import materials as M
 f32 = np.float32
 
 
+class SceneInstance:
+    """A mesh pushed by Scene.push_instance: its medium-interface index and its triangle range in the flattened soup."""
+
+    __slots__ = ("mi_idx", "first_tri", "n_tris")
+
+    def __init__(self, mi_idx, first_tri, n_tris):
+        self.mi_idx, self.first_tri, self.n_tris = mi_idx, first_tri, n_tris
+
+    def __repr__(self):
+        return "SceneInstance(mi_idx=%d, first_tri=%d, n_tris=%d)" % (self.mi_idx, self.first_tri, self.n_tris)
+
+
+def _affine_3x4(m4x4):
+    """The 3x4 row-major affine part of a 4x4 transform; refuses what hk_scene_set_transform would refuse (ValueError)."""
+    m = np.asarray(m4x4, dtype=np.float64)
+    if m.shape != (4, 4):
+        raise ValueError("transform must be a 4x4 matrix, got shape %s" % (m.shape,))
+    if not np.isfinite(m).all():
+        raise ValueError("transform has non-finite entries")
+    if not (m[3] == (0.0, 0.0, 0.0, 1.0)).all():
+        raise ValueError("transform is not affine: its last row must be [0, 0, 0, 1]")
+    m34 = np.ascontiguousarray(m[:3], dtype=f32)
+    if not np.isfinite(m34).all():
+        raise ValueError("transform entries overflow binary32")
+    A3 = m34[:, :3].astype(np.float64)
+    c0 = A3[1, 1] * A3[2, 2] - A3[1, 2] * A3[2, 1]
+    c1 = A3[1, 2] * A3[2, 0] - A3[1, 0] * A3[2, 2]
+    c2 = A3[1, 0] * A3[2, 1] - A3[1, 1] * A3[2, 0]
+    det = (A3[0, 0] * c0 + A3[0, 1] * c1) + A3[0, 2] * c2
+    if not (det != 0.0 and np.isfinite(det)):
+        raise ValueError("transform is singular")
+    return m34
+
+
 def _luminance(c):
     return float(f32(0.212671) * f32(c[0]) + f32(0.715160) * f32(c[1]) + f32(0.072169) * f32(c[2]))
 
@@ -33,6 +67,7 @@ class Scene:
         self._desc = None
         self._keep = None
         self._device = {}           # id(ctx) -> hk_scene handle (owned: released by close() / the next sync())
+        self._transforms = {}       # (first_tri, n_tris) -> 3x4 float32: applied to every device scene after hk_scene_create
         self.bounds = None
 
     # ---- push! ---------------------------------------------------------------------------------
@@ -89,6 +124,78 @@ class Scene:
         self._meshes.append((world, metas))
         self._desc = None
         return mi_idx
+
+    # ---- instances and in-place edits (update_transform!, update_material!) -------------------------------------------------
+    def n_triangles(self):
+        return sum(m.n_faces for m, _ in self._meshes)
+
+    def push_instance(self, mesh, material, transform=None):
+        """push! of a mesh that can be moved later: the description carries the mesh UN-transformed and the library applies
+        `transform` (4x4 affine) after hk_scene_create.  Returns a SceneInstance for set_transform."""
+        m34 = None if transform is None else _affine_3x4(transform)
+        first = self.n_triangles()
+        mi_idx = self.push(mesh, material)
+        inst = SceneInstance(mi_idx, first, mesh.n_faces)
+        if m34 is not None and inst.n_tris > 0:
+            self._transforms[(first, inst.n_tris)] = m34
+        return inst
+
+    def set_transform(self, instance, m4x4):
+        """update_transform!: the instance's triangles become m4x4 applied to the mesh as pushed, in every device scene already
+        created from this Scene and in those created later."""
+        if not isinstance(instance, SceneInstance):
+            raise TypeError("set_transform takes the SceneInstance push_instance returned")
+        m34 = _affine_3x4(m4x4)
+        if instance.n_tris < 1 or instance.first_tri < 0 or instance.first_tri + instance.n_tris > self.n_triangles():
+            raise ValueError("instance %r is not a triangle range of this scene" % (instance,))
+        self._transforms[(instance.first_tri, instance.n_tris)] = m34
+        from . import _lib
+        for h in (getattr(self, "_device", None) or {}).values():
+            _lib.check(_lib.lib().hk_scene_set_transform(h, instance.first_tri, instance.n_tris, m34.ctypes.data_as(A.PF)), "hk_scene_set_transform")
+
+    def _apply_transforms(self, handle):
+        from . import _lib
+        for (first, n), m34 in self._transforms.items():
+            _lib.check(_lib.lib().hk_scene_set_transform(handle, first, n, m34.ctypes.data_as(A.PF)), "hk_scene_set_transform")
+
+    def update_material(self, mi_idx, new_material):
+        """update_material!(scene, idx, material) (scene.jl:104-112): the BSDF material of medium interface `mi_idx` (what push
+        returned) is replaced by one of the same type.  Textures must be constants or Texture objects already in the scene."""
+        if not 0 <= mi_idx < len(self.media_interfaces):
+            raise IndexError("medium interface index %d out of range" % mi_idx)
+        flat = self.media_interfaces[mi_idx][0]
+        plan = []                               # (flat index, material) in record order
+        self._plan_material_update(flat, new_material, plan)
+        n_tex, n_spec = len(self.textures), len(self.spectra)
+        try:
+            recs = [(idx, self._material_record(m, self._material_keys[idx], None)) for idx, m in plan]
+            added = len(self.textures) != n_tex or len(self.spectra) != n_spec
+        finally:
+            del self.textures[n_tex:], self.spectra[n_spec:]
+        if added:
+            raise ValueError("update_material: the new material references a texture or spectrum that is not in the scene")
+        for idx, r in recs:
+            if _alpha_tested(r) != _alpha_tested(self._material_record(self.materials[idx], self._material_keys[idx], None)):
+                raise ValueError("update_material: a Matte material cannot change between opaque and alpha-tested")
+        for idx, m in plan:
+            self.materials[idx] = m
+        kept = self._desc.materials if self._desc is not None else None
+        from . import _lib
+        for idx, r in recs:
+            if kept is not None:
+                kept[idx] = r
+            for h in (getattr(self, "_device", None) or {}).values():
+                _lib.check(_lib.lib().hk_scene_update_materials(h, idx, 1, C.byref(r)), "hk_scene_update_materials")
+
+    def _plan_material_update(self, flat, new, plan):
+        old = self.materials[flat]
+        if isinstance(new, (M.MediumInterface, M.Emissive)) or type(new) is not type(old):
+            raise TypeError("update_material: %s cannot replace %s (the type must match; emission is not editable)" % (type(new).__name__, type(old).__name__))
+        if isinstance(new, M.MixMaterial):
+            new._idx1, new._idx2 = old._idx1, old._idx2
+            self._plan_material_update(old._idx1, new.material1, plan)
+            self._plan_material_update(old._idx2, new.material2, plan)
+        plan.append((flat, new))
 
     @staticmethod
     def _emission_info(material):
@@ -376,6 +483,11 @@ class Scene:
     def world_radius(self):
         self.desc
         return self.bounds[3]
+
+
+def _alpha_tested(rec):
+    """The opacity class hk_scene_create derives from a record (Matte with an alpha texture or alpha < 1)."""
+    return rec.kind == A.HK_MAT_MATTE and (rec.rgb[0].tex >= 0 or rec.rgb[0].c[3] < 1.0)
 
 
 def _media_records(media):

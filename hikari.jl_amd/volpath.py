@@ -130,6 +130,9 @@ def scene_handle(ctx, scene):
         h = C.c_void_p()
         _lib.check(_lib.lib().hk_scene_create(ctx.h, C.byref(d), C.byref(h)), "hk_scene_create")
         dev[id(ctx)] = h
+        apply = getattr(scene, "_apply_transforms", None)
+        if apply is not None:
+            apply(h)                        # instances placed by push_instance / set_transform
     return dev[id(ctx)]
 
 

@@ -345,6 +345,32 @@ int32_t hk_trim_cache(hk_ctx* ctx);
 int32_t hk_scene_create(hk_ctx* ctx, const hk_scene_desc* desc, hk_scene** out);
 int32_t hk_scene_destroy(hk_scene* scene);
 
+/* ---------------------------------------------------------------------------------------------
+ * Editing a scene in place (update_transform!, src/surface_interaction.jl:413-423; update_material!, src/scene.jl:104-112).
+ * Both calls first render the noted calls (see hk_render: they were made against the scene as it was), then enqueue their work on
+ * ctx's stream behind everything already enqueued, and return without waiting for the device.  Films are not cleared.  A refused
+ * call (HK_ERR_INVALID, hk_last_error says why) leaves the scene untouched.
+ *
+ * hk_scene_set_transform: the world positions, normals and tangents of triangles [first_tri, first_tri + n_tris) become m34 (3x4
+ * row-major affine) applied to the values those triangles had at hk_scene_create ("base"); the BVH keeps its topology and its boxes
+ * are refit on the device (traversal slows after large moves: recreate the scene then).  Area lights and the light BVH stay as
+ * created (they are built from the un-transformed mesh, Q18).  Binary32 without contraction, in this order:
+ *   points    p'[k] = ((m[k][0]*x + m[k][1]*y) + m[k][2]*z) + m[k][3]
+ *   normals   A = m[:, 0..2]; C[i][j] = A[i+1][j+1]*A[i+2][j+2] - A[i+1][j+2]*A[i+2][j+1] (indices mod 3) and
+ *             det = (A[0][0]*C[0][0] + A[0][1]*C[0][1]) + A[0][2]*C[0][2] in double; N[i][j] = (float)(C[i][j] / det);
+ *             n'[k] = (N[k][0]*nx + N[k][1]*ny) + N[k][2]*nz, then n' / sqrt((n'x*n'x + n'y*n'y) + n'z*n'z) (division and square root
+ *             correctly rounded); a normal with a NaN component (none given) is kept as it is
+ *   tangents  as normals with A in place of N
+ *   identity  an m34 that is exactly [I | 0] copies the base values back (the scene as created, bit for bit)
+ * Refused: a null pointer, a scene without triangles, n_tris < 1 or a range outside the scene, a non-finite or singular m34.
+ *
+ * hk_scene_update_materials: material records [first, first + n) of hk_scene_desc::materials are replaced by materials[0 .. n-1]
+ * (upload through pinned memory owned by the scene).  Refused: a null pointer, n < 1 or a range outside the scene, and a record that
+ * changes its kind, a Mix's children (i[0], i[1], mix_key), its opacity class (Matte with an alpha texture or alpha < 1) or names a
+ * texture / spectrum index that is out of range. */
+int32_t hk_scene_set_transform(hk_scene* scene, int32_t first_tri, int32_t n_tris, const float* m34);
+int32_t hk_scene_update_materials(hk_scene* scene, int32_t first, int32_t n, const hk_material* materials);
+
 int32_t hk_integrator_create(hk_ctx* ctx, const hk_integrator_params* params, hk_integrator** out);
 int32_t hk_integrator_destroy(hk_integrator* integ);
 
@@ -367,7 +393,8 @@ int32_t hk_film_clear(hk_film* film); /* clear!(vp), volpath.jl:108-113 */
  *     be NOTED: calls that continue each other (same scene / integrator / film / camera / pixel range / stride, sample indices
  *     following on) are rendered as ONE pass — bit-identical film, a seventh of the time — when the note reaches HK_BATCH_PATHS_M
  *     (64 M paths), when a call comes that does not continue it, or when anything looks: hk_flush, hk_sync, every hk_film_* / hk_stats_* /
- *     hk_*_destroy / hk_ctx_set_option entry point.  hk_flush enqueues the noted calls without waiting for them.
+ *     hk_*_destroy / hk_ctx_set_option /
+ *     hk_scene_set_transform / hk_scene_update_materials entry point.  hk_flush enqueues the noted calls without waiting for them.
  *     HK_BATCH_PATHS_M=0 (hk_ctx_set_option) turns the noting off.
  * Argument errors are reported by the call itself; a device error of a deferred pass by the call that flushes it — also by the
  * destroy entry points, which still destroy their object. */
