@@ -1,7 +1,8 @@
 """Multi-GPU behind the C-ABI: pixel-tile sharding (hk_render_tile) and the in-library RCCL film
 reduce (hk_comm_* / hk_film_reduce).  One GPU is all the test box has, so the -m gpu part runs the partitions sequentially on
-cuda:0 (every rank's work is independent by construction) and RCCL as a 1-rank communicator; the 2-rank exchange itself is
-covered on CPU over gloo with the oracle standing in for the device (the product never runs on the CPU)."""
+cuda:0 (every rank's work is independent by construction) and real RCCL as a 1-rank communicator.  The sharding arithmetic of a
+2-rank exchange is covered on CPU over gloo with the oracle standing in for the device (the product never runs on the CPU);
+hk_film_reduce itself runs with 2 and 3 ranks on cuda:0 against a test double of librccl in tests/test_film_reduce_ranks.py."""
 import ctypes as C
 import os
 import subprocess
