@@ -5,6 +5,7 @@
 // the device back inside a frame: queue sizes stay in HBM and every kernel sizes itself from them.
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -21,46 +22,9 @@
 
 #include "bvh_build.h"
 #include "hikari_mi355x.h"
+#include "hk_launch.h"
 #include "hk_nanovdb.h"
 #include "hk_types.h"
-
-namespace hk {
-void launch_camera(hipStream_t, int, const DPathState&, const DFrame&, const DTables&, const DFilter&, const DCamera&, const DSobol&, int);
-void launch_trace(hipStream_t, int, const DPathState&, const DScene&, const DTables&, const DFrame&, int, DStats*);
-void launch_shadow(hipStream_t, int, const DPathState&, const DScene&, const DTables&, const DFrame&, int, DStats*);
-void launch_escaped(hipStream_t, int, const DPathState&, const DScene&, const DTables&, const DFrame&, int);
-void launch_medium(hipStream_t, int, const DPathState&, const DScene&, const DTables&, const DFrame&, const DSobol&, int, DStats*);
-void launch_detect_camera_medium(hipStream_t, const DPathState&, const DScene&, float, float, float, DStats*);
-void launch_shade(hipStream_t, int, int, const DPathState&, const DScene&, const DTables&, const DFrame&, const DSobol&, int, int, DStats*);
-bool grey_compact_ok(const DScene&);
-bool preselect_lights(const DScene&, const DPathState&);
-bool small_pass_fusable(const DScene&, uint32_t);
-bool launch_small_pass(hipStream_t, int, const DPathState&, const DScene&, const DTables&, const DFrame&, const DFilter&, const DCamera&, const DSobol&, int, uint32_t, DStats*, bool, void*, int);
-void launch_light_select(hipStream_t, int, const DPathState&, const DScene&, const DTables&, const DFrame&, const DSobol&, int, uint32_t, DStats*);
-void launch_film(hipStream_t, const DPathState&, const DFrame&, const DTables&, void*, bool);
-void launch_segment_lists(hipStream_t, const DPathState&, int, const int*, const int*);
-void launch_finalize(hipStream_t, const void*, bool, float*, int, int);
-void launch_test_trace(hipStream_t, const DScene&, int, const float*, const float*, const float*, float*, int*, float*);
-void launch_test_sobol(hipStream_t, const DTables&, const DSobol&, int, const int*, const int*, const int*, const int*, float*, float*);
-void launch_test_camera(hipStream_t, const DTables&, const DFilter&, const DCamera&, const DSobol&, int, int, const int*, const int*, const int*, float*);
-void launch_test_uplift(hipStream_t, const DTables&, int, int, const float*, const float*, float*);
-void launch_test_light_bvh(hipStream_t, const DScene&, int, const float*, const float*, const float*, int*, float*, const int*, float*);
-void launch_aux(hipStream_t, const DScene&, const DCamera&, int, int, float, float*, float*, float*);
-void launch_postprocess(hipStream_t, const hk_postprocess_params&, const float*, const float*, float*, int, int);
-void launch_denoise_variance(hipStream_t, const float*, float*, int, int);
-void launch_denoise_atrous(hipStream_t, const hk_denoise_params&, int, const float*, const float*, const float*, const float*, float*, int, int);
-void launch_sobol_table(hipStream_t, const DSobol&, const DFrame&, uint2*, int);
-void launch_sobol_lo_table(hipStream_t, const DSobol&, const DFrame&, uint16_t*, int, int, int, int);
-void launch_test_light(hipStream_t, const DScene&, const DTables&, int, int, int, const float*, const float*, const float*, float*);
-void launch_test_bsdf(hipStream_t, const DScene&, const DTables&, int, int, int, int, const float*, const float*, const float*, const float*, const float*, const float*, float*);
-void launch_test_mix(hipStream_t, const DScene&, int, int, const float*, const float*, const float*, int*);
-void launch_test_medium(hipStream_t, const DScene&, const DTables&, int, int, int, const float*, const float*, const float*, const float*, float*);
-int test_majorant_stride();
-void launch_test_trace_lean(hipStream_t, int, const DScene&, int, int, const float*, const float*, const float*, float*, int*, float*);
-void launch_slot_of_prim(hipStream_t, const float4*, int, int*);
-void launch_xform_tris(hipStream_t, const DXform&, int, int, const float*, const float*, const float*, const int*, float*, float*, float*, float*, float4*);
-void launch_refit_level(hipStream_t, int, int, DNode*, DQNode*, const DQGrid&, const float4*, const float*);
-}  // namespace hk
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) {
@@ -433,7 +397,7 @@ extern "C" int32_t hk_ctx_create(int32_t device_id, void* stream, hk_ctx** out) 
         if (const char* e = std::getenv(name)) c->knobs.kv[name] = e;
     KnobScope knobs(&c->knobs);
     {
-        if (const char* e = hk::knob("HK_WAVES_PER_CU")) c->waves_per_cu = std::atoi(e) > 0 ? std::atoi(e) : 0;
+        c->waves_per_cu = hk::knob_int_in("HK_WAVES_PER_CU", 1, INT_MAX, 0);
         c->stat_rows = c->n_cu * 32 * 2;   // second half: the kernels of the second stream (their waves have the same physical ids)
         if (const char* e = hk::knob("HK_OVERLAP")) c->overlap = std::atoi(e) ? 1 : 0;
         else c->overlap = -1;
@@ -744,9 +708,7 @@ extern "C" int32_t hk_scene_create(hk_ctx* c, const hk_scene_desc* d, hk_scene**
     // ---- BVH ----
     hk::BVH bvh;
     {
-        const char* leaf = hk::knob("HK_BVH_LEAF");
-        const char* bins = hk::knob("HK_BVH_BINS");
-        hk::build_bvh(d->positions, T, bvh, leaf ? std::atoi(leaf) : 4, bins ? std::atoi(bins) : 32);
+        hk::build_bvh(d->positions, T, bvh, hk::knob_int("HK_BVH_LEAF", 4), hk::knob_int("HK_BVH_BINS", 32));
     }
     s->bvh_nodes = (int)bvh.nodes.size();
     s->bvh_leaf_tris = (int)bvh.leaf_prims.size();
@@ -782,10 +744,9 @@ extern "C" int32_t hk_scene_create(hk_ctx* c, const hk_scene_desc* d, hk_scene**
     float q_base[3] = {0, 0, 0}, q_cell[3] = {1, 1, 1};
     bool have_qnodes = false;
     {
-        const char* qk = hk::knob("HK_QNODES");
         // (shallow trees gain nothing: their any-hit kernel with the nodes beyond its LDS cache read from a quantised array — measured,
         //  Cornell shadow class + 1.7 %, two-spheres + 0.7 % — is bound by instruction issue, and the conversions are instructions)
-        if (bvh.max_depth > 16 && !bvh.nodes.empty() && (!qk || std::atoi(qk) != 0)) {
+        if (bvh.max_depth > 16 && !bvh.nodes.empty() && hk::knob_on("HK_QNODES")) {
             for (int k = 0; k < 3; ++k) {
                 const double ext = (double)bvh.hi[k] - (double)bvh.lo[k];
                 q_cell[k] = (float)std::max(ext / 65527.0, 1e-30);
@@ -1752,9 +1713,9 @@ extern "C" int32_t hk_film_read_rgb(hk_ctx* c, hk_film* f, float* out) {
     // itself is freed — a C host that mallocs a frame buffer per frame gets the same address back, and the copy would go through a
     // stale registration): hk_film_pin_host names the buffer, or HK_READBACK_PIN=1 brings back "the same pointer twice in a row".
     // A registration that failed is remembered for that pointer and not tried again on every frame.
-    const char* pin = hk::knob("HK_READBACK_PIN");
+    const bool pin = hk::knob_int("HK_READBACK_PIN", 0) == 1;
     if (!f->pinned_explicit) {
-        if (pin && std::atoi(pin) == 1 && f->pinned_user != out && f->last_out == out && f->pin_failed != out) {
+        if (pin && f->pinned_user != out && f->last_out == out && f->pin_failed != out) {
             if (f->pinned_user) (void)hipHostUnregister(f->pinned_user);
             f->pinned_user = hipHostRegister(out, bytes, hipHostRegisterDefault) == hipSuccess ? out : nullptr;
             if (!f->pinned_user) f->pin_failed = out;
@@ -1906,7 +1867,7 @@ hipError_t alloc_arr(hk_integrator* I, T*& dst, size_t n) {
 //   surfaces, open scene      static stride, 48 per CU   (sky: most paths escape after 1-2 vertices; finer segments only fragment
 //                             the per-kind queues: k_shade +7 % at 96, +15 % at 256, whichever way they are handed out)
 // HK_WAVES_PER_CU / HK_DYNAMIC_SEGMENTS override.  stats rows are indexed by PHYSICAL wave (ctx->stat_rows).
-int ensure_state(hk_integrator* I, int capacity, bool media, bool open_scene, bool small_scene, bool grey_compact, hipStream_t users = nullptr, bool fusable = false, bool opaque_surfaces = false) {
+int ensure_state(hk_integrator* I, int capacity, bool media, bool open_scene, bool small_scene, bool grey_compact, hipStream_t users = nullptr, bool fusable = false, bool lean = false) {   // lean: hk::lean_scene (it implies !media)
     const int n_cu = I->ctx->n_cu;
     // a closed scene's pass of at most HK_MID_PASS_PATHS_M (48) million paths — a rank's share of a frame under 8-way strong scaling —
     // behaves like the open scene WHEN THE SCENE IS SMALL (BVH depth <= 16, the Cornell box): the deep bounces hold a few dozen rays per
@@ -1921,37 +1882,31 @@ int ensure_state(hk_integrator* I, int capacity, bool media, bool open_scene, bo
     long W_want = ((long)(capacity + 63) / 64) / 16;
     if (W_want < 4L * n_cu) W_want = 4L * n_cu;
     if (W_want > cap_per_cu * n_cu) W_want = cap_per_cu * n_cu;
-    {   // read per call (tests toggle it); an unset knob is the built-in policy again — not the last forced count
-        const char* e = hk::knob("HK_WAVES_PER_CU");
-        I->ctx->waves_per_cu = e && std::atoi(e) > 0 ? std::atoi(e) : 0;
-    }
+    // read per call (tests toggle it); an unset knob is the built-in policy again — not the last forced count
+    I->ctx->waves_per_cu = hk::knob_int_in("HK_WAVES_PER_CU", 1, INT_MAX, 0);
     if (I->ctx->waves_per_cu > 0) W_want = (long)I->ctx->waves_per_cu * n_cu;
     W_want = (W_want + 3) / 4 * 4;
     I->st.dynamic_segments = (media || (!open_scene && !mid)) ? 1 : 0;
-    if (const char* e = hk::knob("HK_DYNAMIC_SEGMENTS")) I->st.dynamic_segments = std::atoi(e) ? 1 : 0;
+    I->st.dynamic_segments = hk::knob_int("HK_DYNAMIC_SEGMENTS", I->st.dynamic_segments) ? 1 : 0;
     I->st.compact = media ? (grey_compact ? 1 : 0) : 1;
-    {   // slim shadow records (HK_SHADOW_FINAL=0: the 60-byte records of rounds 3-5; A/B switch, films bit-identical)
-        const char* e = hk::knob("HK_SHADOW_FINAL");
-        I->st.sh_final = (!media && opaque_surfaces && !(e && std::atoi(e) == 0)) ? 1 : 0;   // (k_shadow's scenes: no medium, no alpha-tested surface)
-        // lean generation records of the same scenes (HK_LEAN_RECORDS=0: 8-byte meta words, depth-0 origins stored; A/B switch, films bit-identical)
-        const char* l = hk::knob("HK_LEAN_RECORDS");
-        I->st.meta32 = (!media && opaque_surfaces && !(l && std::atoi(l) == 0)) ? 1 : 0;
-        I->st.const_origin = 0;   // (per call: render_tile_now knows the camera)
-    }
-    I->st.ticket_share = 1;
-    if (const char* e = hk::knob("HK_TICKET_SHARE")) I->st.ticket_share = std::atoi(e) ? 1 : 0;
+    // slim shadow records of k_shadow's scenes (HK_SHADOW_FINAL=0: the 60-byte records of rounds 3-5; A/B switch, films bit-identical)
+    I->st.sh_final = (lean && hk::knob_on("HK_SHADOW_FINAL")) ? 1 : 0;
+    // lean generation records of the same scenes (HK_LEAN_RECORDS=0: 8-byte meta words, depth-0 origins stored; A/B switch, films bit-identical)
+    I->st.meta32 = (lean && hk::knob_on("HK_LEAN_RECORDS")) ? 1 : 0;
+    I->st.const_origin = 0;   // (per call: render_tile_now knows the camera)
+    I->st.ticket_share = hk::knob_int("HK_TICKET_SHARE", 1) ? 1 : 0;
     {   // a SMALL pass (at most 16 chunks for each of 4 waves per CU: a one-sample call at 800^2) hands segment g to wave g of every launch
         // (static stride where a grid is smaller): the 17 k_segment_lists launches of a call and the ticket round trips go, and the segment
         // count no longer has to stay below every kernel's residency, so it can be as fine as the latency of one wave's chunk wants it —
         // HK_SMALL_PASS_WAVES per CU.  HK_SMALL_PASS=0: lists and tickets as ever.
-        const char* e = hk::knob("HK_SMALL_PASS");
-        const bool small = W_want <= 4L * n_cu && !(e && std::atoi(e) == 0) && hk::knob("HK_DYNAMIC_SEGMENTS") == nullptr;   // (an explicit HK_DYNAMIC_SEGMENTS keeps lists / tickets: the tests' small films)
+        const bool small_on = hk::knob_on("HK_SMALL_PASS");
+        const bool small = W_want <= 4L * n_cu && small_on && hk::knob("HK_DYNAMIC_SEGMENTS") == nullptr;   // (an explicit HK_DYNAMIC_SEGMENTS keeps lists / tickets: the tests' small films)
         I->st.small_pass = small ? 1 : 0;
-        if (mid && I->st.dynamic_segments == 0 && !(e && std::atoi(e) == 0) && !(hk::knob("HK_MID_LISTS") && std::atoi(hk::knob("HK_MID_LISTS"))))
+        if (mid && I->st.dynamic_segments == 0 && small_on && !hk::knob_int("HK_MID_LISTS", 0))
             I->st.small_pass = 1;   // a mid-size pass of a closed scene: its 48 segments per CU all hold paths down to the last bounce — the work lists (17 launches) list everything
         if (small) {
             I->st.dynamic_segments = 0;
-            const char* w = hk::knob("HK_SMALL_PASS_WAVES");
+            const int w = hk::knob_int_in("HK_SMALL_PASS_WAVES", 1, INT_MAX, 0);
             // (800^2, one sample per call.  Eight calls in flight on eight lanes (HK_PIPELINE): Cornell 0.99 / 0.89 / 1.03 / 1.30 ms per call at
             // 4 / 8 / 16 / 32 segments per CU, cloud 12.6 / 13.8 / 17.9 / 19.6.  ONE call at a time — the default since small calls are batched,
             // and what a caller that looks at every frame gets: Cornell 2.04 / 1.53 / 1.41 / 1.34 / 1.59 / 1.63 ms at 4 / 8 / 12 / 16 / 20 / 32,
@@ -1960,14 +1915,13 @@ int ensure_state(hk_integrator* I, int capacity, bool media, bool open_scene, bo
             // trace blocks covered half of the CUs.  An OPEN surface scene keeps 8: its deep bounces are empty and its glass / conductor
             // shade kernels hold fewer than 16 waves per CU.)
             // k_small_pass (`fusable`: the whole pass in one launch) likes 8: 1.05 ms against 1.14 at 16 — fuller chunks, no spills at two waves per SIMD.
-            long per_cu = w && std::atoi(w) > 0 ? std::atoi(w) : (users ? (media ? 4 : 8) : (((open_scene && !media) || fusable) ? 8 : 16));
+            long per_cu = w > 0 ? w : (users ? (media ? 4 : 8) : (((open_scene && !media) || fusable) ? 8 : 16));
             const long chunks = ((long)capacity + 63) / 64;
             while (per_cu > 4 && per_cu * n_cu > chunks) per_cu /= 2;   // (no segment without a chunk)
             if (I->ctx->waves_per_cu <= 0) W_want = (per_cu * n_cu + 3) / 4 * 4;
         }
     }
-    const char* split_env = hk::knob("HK_WALK_SPLIT");
-    const bool want_split = media && split_env && std::atoi(split_env);
+    const bool want_split = media && hk::walk_split_mode();
     // the retained state must be of the same flavour: a state allocated for a scene with media has no sel_light (k_light_select would
     // silently not run in a later scene without media), one allocated without HK_WALK_SPLIT has no hand-over queues
     if (I->st_capacity >= capacity && I->st_depth >= I->p.max_depth && I->st.n_waves == (int)W_want && I->st_media == (media ? 1 : 0) && (!want_split || I->st.wq_a != nullptr)) return HK_OK;
@@ -2039,8 +1993,7 @@ int ensure_state(hk_integrator* I, int capacity, bool media, bool open_scene, bo
         HIP_TRY(alloc_arr(I, s.seg_list_n, (size_t)(I->p.max_depth + 2) * Q_COUNT));
         return HK_OK;
     };
-    const char* slab_env = hk::knob("HK_STATE_SLAB");   // (0: one allocation per array, nothing cached)
-    if (!(slab_env && std::atoi(slab_env) == 0)) {
+    if (hk::knob_on("HK_STATE_SLAB")) {   // (0: one allocation per array, nothing cached)
         I->slab_mode = 1, I->slab_off = 0;
         if (int e = layout()) {
             I->slab_mode = 0;
@@ -2147,8 +2100,7 @@ extern "C" int32_t hk_render_tile(hk_ctx* c, hk_scene* sc, hk_integrator* I, hk_
         hk_ctx::Pending& p = c->pending;
         // A caller that owns the stream or the accumulators may order its own work behind this call with stream / event calls the library
         // never sees (torch.cuda.synchronize(), a reduce of the accumulators): its calls are enqueued at once.  HK_DEFER_EXTERNAL=1: batched all the same.
-        const char* de = hk::knob("HK_DEFER_EXTERNAL");
-        const bool visible_order = (c->own_stream_order && !film->external && !film->exposed) || (de && std::atoi(de));
+        const bool visible_order = (c->own_stream_order && !film->external && !film->exposed) || hk::knob_int("HK_DEFER_EXTERNAL", 0);
         const bool small = batch_paths > 0 && visible_order && !c->time_kernels && (long)n_samples * px <= small_paths && I->p.samples_per_pass <= 0;
         if (p.active && small && p.sc == sc && p.I == I && p.film == film && std::memcmp(&p.cam, cam, sizeof(hk_camera)) == 0 && p.stride == sample_stride && p.x0 == x0 &&
             p.y0 == y0 && p.x1 == x1 && p.y1 == y1 && (long)p.first + (long)p.n * p.stride == first_sample_idx && (long)(p.n + n_samples) * px <= batch_paths) {
@@ -2204,7 +2156,7 @@ static int render_tile_now(hk_ctx* c, hk_scene* sc, hk_integrator* I, hk_film* f
         // the lanes' path-state sets together stay below 8 GB (440 B per path)
         int n_lanes = 1;   // (off since small calls are batched — HK_PIPELINE = 2 .. 16 turns the lanes on for calls that cannot be: a read-back between them)
         long max_paths = 8L << 20;
-        if (const char* e = hk::knob("HK_PIPELINE")) n_lanes = std::atoi(e) >= 1 && std::atoi(e) <= 16 ? std::atoi(e) : n_lanes;
+        n_lanes = hk::knob_int_in("HK_PIPELINE", 1, 16, n_lanes);
         if (const char* e = hk::knob("HK_PIPELINE_MAX_PATHS_M")) max_paths = std::atol(e) > 0 ? std::atol(e) << 20 : max_paths;
         {
             const long by_memory = (8L << 30) / (440L * (long)S * fr.n_pixels_padded);
@@ -2214,7 +2166,7 @@ static int render_tile_now(hk_ctx* c, hk_scene* sc, hk_integrator* I, hk_film* f
         // handful, does not start them: only a run of HK_PIPELINE_AFTER = 4 small calls in a row does, i.e. a progressive viewer)
         const bool small_call = n_samples <= S && (long)S * fr.n_pixels_padded <= max_paths;
         int after = 4;
-        if (const char* e = hk::knob("HK_PIPELINE_AFTER")) after = std::atoi(e) >= 0 ? std::atoi(e) : after;
+        after = hk::knob_int_in("HK_PIPELINE_AFTER", 0, INT_MAX, after);
         c->small_streak = small_call ? c->small_streak + 1 : 0;
         const bool lanes_started = c->ev_main != nullptr;
         if (n_lanes > 1 && !c->time_kernels && small_call && (lanes_started || c->small_streak > after)) {
@@ -2251,7 +2203,7 @@ static int render_tile_now(hk_ctx* c, hk_scene* sc, hk_integrator* I, hk_film* f
                           // (the predicate of launch_small_pass, as far as it is known here: a call of >= 16 samples draws from the sample-bit table
                           // and keeps the launches — those want 16 segments per CU, not k_small_pass's 8)
                           !piped && !c->time_kernels && !c->count_nodes && n_samples < 16 && hk::small_pass_fusable(sc->d, sc->kinds_mask),
-                          sc->d.all_opaque != 0 && sc->d.n_media == 0);
+                          hk::lean_scene(sc->d));
     if (st != HK_OK) return st;
     I->st.const_origin = (I->st.meta32 && !(cam->lens_radius > 0)) ? 1 : 0;   // a pinhole camera: generate_ray gives every path the same origin (hk_device.h), stored once per segment
     fr.sample_stride = sample_stride;
@@ -2261,17 +2213,9 @@ static int render_tile_now(hk_ctx* c, hk_scene* sc, hk_integrator* I, hk_film* f
     fr.count_nodes = c->count_nodes;
     fr.implicit_ones = sc->d.n_media == 0 ? 1 : 0;
     {   // loop shapes of the tracking state machines (measured defaults; read per call)
-        auto knob = [](const char* name, int dflt) {
-            const char* e = hk::knob(name);
-            const int v = e ? std::atoi(e) : dflt;
-            return v >= 1 && v <= 255 ? v : dflt;
-        };
-        {   // collision rounds of k_track_flat wait for HK_TRACK_MIN_PENDING lanes, for at most HK_TRACK_EXTRA_ADVANCE further cheap steps (0 = never wait)
-            const char* e = hk::knob("HK_TRACK_MIN_PENDING");
-            const char* x = hk::knob("HK_TRACK_EXTRA_ADVANCE");
-            const int mp = e ? std::atoi(e) : 0, xa = x ? std::atoi(x) : 4;
-            fr.track_gate = (mp >= 0 && mp <= 64 ? mp : 0) | ((xa >= 0 && xa <= 255 ? xa : 4) << 8);
-        }
+        auto knob = [](const char* name, int dflt) { return hk::knob_int_in(name, 1, 255, dflt); };
+        // collision rounds of k_track_flat wait for HK_TRACK_MIN_PENDING lanes, for at most HK_TRACK_EXTRA_ADVANCE further cheap steps (0 = never wait)
+        fr.track_gate = hk::knob_int_in("HK_TRACK_MIN_PENDING", 0, 64, 0) | (hk::knob_int_in("HK_TRACK_EXTRA_ADVANCE", 0, 255, 4) << 8);
         fr.delta_advance = knob("HK_DELTA_ADVANCE", 3);
         fr.refill_idle = knob("HK_TRACK_REFILL_IDLE", 24);
         fr.walk_tune = knob("HK_SHADOW_TRACK_BATCH", 8) | (knob("HK_TRACK_ADVANCE", 2) << 8) | (knob("HK_SHADOW_FEED_ROUNDS", 3) << 16) | ((knob("HK_WALK_REFILL_IDLE", 16) > 63 ? 63 : knob("HK_WALK_REFILL_IDLE", 16)) << 24);

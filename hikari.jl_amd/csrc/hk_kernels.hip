@@ -4711,170 +4711,6 @@ __global__ void __launch_bounds__(HK_TRACE_BLOCK) k_aux(DScene sc, DCamera cam, 
 }
 
 // ---------------------------------------------------------------------------------------------------
-// sub-kernel entry points used by the parity tests
-// ---------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(HK_TRACE_BLOCK) k_test_trace(DScene sc, int n, const float* o3, const float* d3, const float* tmax, float* out_t, int* out_prim,
-                                                               float* out_uv) {
-    __shared__ int lds_stack[(HK_TRACE_BLOCK / 64) * HK_LDS_STACK * 64];
-    int* stack = lds_stack + (threadIdx.x >> 6) * (HK_LDS_STACK * 64);
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        unsigned a = 0, b = 0;
-        bool dummy;
-        HitRec h = traverse<0, false>(sc, mk3(o3[3 * i], o3[3 * i + 1], o3[3 * i + 2]), mk3(d3[3 * i], d3[3 * i + 1], d3[3 * i + 2]), tmax[i], stack, lane_id(), a, b,
-                                      dummy);
-        out_t[i] = h.prim >= 0 ? h.t : INF_F;
-        out_prim[i] = h.prim;
-        out_uv[2 * i] = h.prim >= 0 ? h.u : 0.0f;
-        out_uv[2 * i + 1] = h.prim >= 0 ? h.v : 0.0f;
-    }
-}
-__global__ void k_test_sobol(DTables T, DSobol sob, int n, const int* px, const int* py, const int* sidx, const int* dim, float* o1, float* o2) {
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        SobolCtx c = sobol_ctx(sob, T.sobol, px[i], py[i], sidx[i]);
-        o1[i] = sobol_1d(c, dim[i]);
-        v2 v = sobol_2d(c, dim[i]);
-        o2[2 * i] = v.x;
-        o2[2 * i + 1] = v.y;
-    }
-}
-__global__ void k_test_camera(DTables T, DFilter flt, DCamera cam, DSobol sob, int height, int n, const int* px, const int* py, const int* sidx, float* out15) {
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        int x = px[i], y = py[i];
-        SobolCtx sc = sobol_ctx(sob, T.sobol, x, y, sidx[i]);
-        float wu = sobol_1d(sc, 1);
-        v2 jit = sobol_2d(sc, 3);
-        float tu = sobol_1d(sc, 4);
-        v2 lens = sobol_2d(sc, 6);
-        float fx, fy, fw;
-        filter_sample(flt, jit, fx, fy, fw);
-        S4 lambda, pdf;
-        sample_wavelengths_visible(wu, lambda, pdf);
-        v2 pfilm = mk2((float)x + 0.5f + fx, (float)height - (float)y + 1.0f + 0.5f + fy);
-        v3 ro, rd;
-        float time;
-        generate_ray(cam, pfilm, lens, tu, ro, rd, time);
-        float* o = out15 + 15 * (size_t)i;
-        o[0] = lambda.x; o[1] = lambda.y; o[2] = lambda.z; o[3] = lambda.w;
-        o[4] = pdf.x; o[5] = pdf.y; o[6] = pdf.z; o[7] = pdf.w;
-        o[8] = fw;
-        o[9] = ro.x; o[10] = ro.y; o[11] = ro.z;
-        o[12] = rd.x; o[13] = rd.y; o[14] = rd.z;
-    }
-}
-__global__ void k_test_uplift(DTables T, int mode, int n, const float* rgb, const float* lam, float* out) {
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        S4 l = s4(lam[4 * i], lam[4 * i + 1], lam[4 * i + 2], lam[4 * i + 3]);
-        float r = rgb[3 * i], g = rgb[3 * i + 1], b = rgb[3 * i + 2];
-        S4 s = mode == 0 ? eval_bounded(coef_bounded(T, r, g, b), l) : (mode == 1 ? eval_scaled(coef_unbounded(T, r, g, b), l) : eval_illuminant(coef_illuminant(T, r, g, b), l));
-        out[4 * i] = s.x;
-        out[4 * i + 1] = s.y;
-        out[4 * i + 2] = s.z;
-        out[4 * i + 3] = s.w;
-    }
-}
-__global__ void k_test_light_bvh(DScene sc, int n, const float* p3, const float* n3, const float* u, int* out_light, float* out_pmf, const int* query, float* out_qpmf) {
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        v3 p = mk3(p3[3 * i], p3[3 * i + 1], p3[3 * i + 2]), nn = mk3(n3[3 * i], n3[3 * i + 1], n3[3 * i + 2]);
-        float pmf;
-        unsigned vis = 0;
-        out_light[i] = bvh_sample_light(sc, p, nn, u[i], pmf, vis);
-        out_pmf[i] = pmf;
-        if (query) out_qpmf[i] = bvh_pmf(sc, p, nn, query[i], vis);
-    }
-}
-
-// resolve_mix_material (mix-material.jl:222-238) for n hit points: out = index of the material a MixMaterial resolves to
-__global__ void k_test_mix(DScene sc, int mat_idx, int n, const float* p3, const float* wo3, const float* uv2, int* out) {
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-        out[i] = resolve_mix_material(sc, mat_idx, mk3(p3[3 * i], p3[3 * i + 1], p3[3 * i + 2]), mk3(wo3[3 * i], wo3[3 * i + 1], wo3[3 * i + 2]), mk2(uv2[2 * i], uv2[2 * i + 1]));
-}
-// media: mode 0 = sample_point (media.jl:1327-1370, 1527-1575; nanovdb.jl:400-469) -> out[13] = sigma_a4, sigma_s4, Le4, g;
-//        mode 1 = majorant iterator along a ray (media.jl:229-340, 625-729) -> out[1 + 3*HK_TEST_MAJ_SEGS] = segment count, then
-//                 (t_min, t_max, sigma_maj[0]) of the first HK_TEST_MAJ_SEGS segments.  Same MM instantiation as the tracking kernels.
-//        mode 2 = the same walk with majorant_skip_zero in front of every majorant_next (what the tracking kernels do): total
-//                 segment count incl. the skipped ones, then the first HK_TEST_MAJ_SEGS segments that were NOT skipped.
-#define HK_TEST_MAJ_SEGS 16
-template <int MM>
-__global__ void k_test_medium(DScene sc, DTables T, int mode, int medium_idx, int n, const float* a3, const float* b3, const float* tmax, const float* lambda, float* out) {
-    const DMedium& med = sc.media[medium_idx];
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const S4 l = s4(lambda[4 * i], lambda[4 * i + 1], lambda[4 * i + 2], lambda[4 * i + 3]);
-        const v3 a = mk3(a3[3 * i], a3[3 * i + 1], a3[3 * i + 2]);
-        const S4 base_a = eval_scaled(med.sigma_a, l), base_s = eval_scaled(med.sigma_s, l), base_Le = eval_scaled(med.Le, l);
-        if (mode == 0) {
-            MediumProps mp = sample_point<MM>(T, l, med, base_a, base_s, base_Le, a);
-            float* r = out + 13 * (size_t)i;
-            r[0] = mp.sigma_a.x, r[1] = mp.sigma_a.y, r[2] = mp.sigma_a.z, r[3] = mp.sigma_a.w;
-            r[4] = mp.sigma_s.x, r[5] = mp.sigma_s.y, r[6] = mp.sigma_s.z, r[7] = mp.sigma_s.w;
-            r[8] = mp.Le.x, r[9] = mp.Le.y, r[10] = mp.Le.z, r[11] = mp.Le.w;
-            r[12] = mp.g;
-        } else {
-            const v3 d = mk3(b3[3 * i], b3[3 * i + 1], b3[3 * i + 2]);
-            float* r = out + (1 + 3 * HK_TEST_MAJ_SEGS) * (size_t)i;
-            for (int k = 0; k < 1 + 3 * HK_TEST_MAJ_SEGS; ++k) r[k] = 0.0f;
-            MajorantIter it = create_majorant_iterator<MM>(med, a, d, tmax[i]);
-            int count = 0, kept = 0;
-            float t0, t1;
-            S4 sm;
-            for (;;) {
-                if (mode == 2) majorant_skip_zero<MM>(it, med, count);   // fast-forward over zero cells (measured and not used by the kernels: DESIGN §5)
-                if (count >= 256 || !majorant_next<MM>(it, med, base_a + base_s, t0, t1, sm)) break;
-                // mode 1 records every segment, mode 2 the segments that survive the fast-forward (zero cells excluded)
-                if (kept < HK_TEST_MAJ_SEGS) r[1 + 3 * kept] = t0, r[2 + 3 * kept] = t1, r[3 + 3 * kept] = sm.x;
-                ++kept;
-                ++count;
-            }
-            r[0] = (float)count;
-        }
-    }
-}
-// The traversal of the surfaces-only bench path: lane_ray_round (while-while rounds, straggler exit, LDS stack of STACK entries)
-// driven by the same per-lane refill as k_trace_lean / k_shadow, over a plain ray array.  Every wave owns a contiguous range of
-// rays.  ANYHIT = the shadow kernel's first-accepted-hit mode (out_prim >= 0 <=> occluded).
-template <bool ANYHIT, int STACK, bool QN = false>
-__global__ void __launch_bounds__(HK_TRACE_BLOCK) k_test_trace_lean(DScene sc, int n, const float* o3, const float* d3, const float* tmax, float* out_t, int* out_prim, float* out_uv) {
-    __shared__ int lds_stack[(HK_TRACE_BLOCK / 64) * STACK * 64];
-    int* stack = lds_stack + (threadIdx.x >> 6) * (STACK * 64);
-    const int lane = lane_id();
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
-    const int DONE = (int)0x80000000;
-    const int waves = physical_waves();
-    const int per_wave = (n + waves - 1) / waves;
-    const int first = global_wave() * per_wave;
-    const int count = first >= n ? 0 : (n - first < per_wave ? n - first : per_wave);
-    unsigned n_nodes = 0, n_tris = 0;
-    int cursor = 0;
-    bool have = false;
-    int idx = 0;
-    LaneRay r;
-    r.cur = r.pend = DONE;
-    for (;;) {
-        const unsigned long long run_m = __ballot(have && r.cur != DONE);
-        if (run_m == 0ull || (64 - __popcll(run_m) >= HK_TRACE_MIN_IDLE && cursor < count)) {
-            if (have && r.cur == DONE) {
-                out_t[idx] = r.best.prim >= 0 ? r.best.t : INF_F;
-                out_prim[idx] = r.best.prim;
-                out_uv[2 * idx] = r.best.prim >= 0 ? r.best.u : 0.0f;
-                out_uv[2 * idx + 1] = r.best.prim >= 0 ? r.best.v : 0.0f;
-                have = false;
-            }
-            const unsigned long long want = __ballot(!have);
-            const int avail = count - cursor;
-            const int rank = __popcll(want & lt_mask);
-            if (!have && rank < avail) {
-                idx = first + cursor + rank;
-                lane_ray_start<QN>(r, sc, mk3(o3[3 * idx], o3[3 * idx + 1], o3[3 * idx + 2]), mk3(d3[3 * idx], d3[3 * idx + 1], d3[3 * idx + 2]), tmax[idx]);
-                have = true;
-            }
-            const int want_n = __popcll(want);
-            cursor += want_n < avail ? want_n : (avail > 0 ? avail : 0);
-            if (__ballot(have) == 0ull) break;
-        }
-        lane_ray_round<ANYHIT, false, 0, (ANYHIT ? HK_POSTPONE_ANYHIT != 0 : HK_POSTPONE_CLOSEST != 0), false, QN>(r, have && r.cur != DONE, sc, stack, lane, n_nodes, n_tris);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
 // denoise! (src/denoise.jl): 3x3 luminance variance (:236-286) and one a-trous pass (:136-229).  Buffers are Julia [h,w]
 // column-major: linear index i = (col-1)*h + (row-1), exactly the reference's idx -> (row, col) mapping.
 // ---------------------------------------------------------------------------------------------------
@@ -5040,633 +4876,6 @@ __global__ void __launch_bounds__(256) k_refit_level(int begin, int end, DNode* 
     }
 }
 
-// ---------------------------------------------------------------------------------------------------
-// launch wrappers (called from hk_api.cpp)
-// ---------------------------------------------------------------------------------------------------
-namespace hk {
 
-#ifndef HK_OCC_SCALE_DEFAULT
-#define HK_OCC_SCALE_DEFAULT 1.0f
-#endif
-static inline int grid_for(int n, int block, int cap) {
-    long g = ((long)n + block - 1) / block;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (int)g;
-}
-
-// blocks per CU that are actually resident for a kernel (occupancy API, capped): the wave-segment loop makes any
-// grid size correct, so the grid is sized to residency instead of oversubscribing and paying a tail round.
-template <class K>
-static int resident_blocks(K kernel, int block) {   // blocks per CU as the occupancy API reports them (uncapped)
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-    return per_cu;
-}
-// HK_OCC_SCALE (round 6): the occupancy API of this ROCm answers HALF of what the register file admits for the 256-thread kernels here
-// (k_camera, 52 VGPRs: 4 blocks per CU where 512 / 56 registers give 8 waves per SIMD = 8 blocks; MI355X_MICROARCH.md "Register files").
-// Grids are sized by `answer x scale`, capped at the caller's cap (8 blocks = 32 waves per CU, the hardware's own limit) — a block the
-// CU cannot hold simply starts later, and the ticketed / strided segment loops make any grid size correct.
-static float occ_scale() {
-    const char* e = hk::knob("HK_OCC_SCALE");
-    const float v = e ? (float)std::atof(e) : HK_OCC_SCALE_DEFAULT;
-    return v >= 0.25f && v <= 8.0f ? v : 1.0f;
-}
-// Residency is a property of (kernel, device): cached per kernel instantiation AND per device, so one process can drive several
-// GPUs (the in-library multi-device path) without one device's answer leaking to another.
-#define HK_MAX_DEVICES 64
-template <auto Kernel>
-static int cached_blocks(int block, int n_cu, int cap_per_cu) {
-    static int cache[HK_MAX_DEVICES];
-    int dev = 0, per_cu;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= HK_MAX_DEVICES)
-        per_cu = resident_blocks(Kernel, block);
-    else {
-        if (cache[dev] == 0) {
-            cache[dev] = resident_blocks(Kernel, block);
-            if (hk::knob("HK_DEBUG_ALLOC")) std::fprintf(stderr, "HK_DEBUG_ALLOC occupancy API: %d blocks of %d per CU for %s\n", cache[dev], block, __PRETTY_FUNCTION__);
-        }
-        per_cu = cache[dev];
-    }
-    per_cu = (int)((float)per_cu * occ_scale() + 0.5f);
-    if (per_cu < 1) per_cu = 1;
-    if (per_cu > cap_per_cu) per_cu = cap_per_cu;
-    return per_cu * n_cu;
-}
-// Segments are walked with a static stride, so the number of physical waves must DIVIDE W or the last round runs with a
-// fraction of the waves (shade at W = 16/CU with 12 resident: 12 % slower than at W = 24): the largest divisor of the
-// 4-wave block count that is resident.
-static int node_cache_mode() {   // HK_NODE_CACHE=0: the lean closest-hit kernel reads every node from global memory (A/B switch, looked up per launch in the context's knob table)
-    const char* e = hk::knob("HK_NODE_CACHE");
-    return (e && std::atoi(e) == 0) ? 0 : 1;
-}
-static int clamp_blocks(int blocks, const DPathState& st, int waves_per_block = 4) {
-    const int units = st.n_waves / waves_per_block;
-    if (blocks >= units) return units;
-    if (st.dynamic_segments) return blocks;
-    int best = 1;
-    for (int b = blocks; b >= 1; --b)
-        if (units % b == 0) {
-            best = b;
-            break;
-        }
-    // a divisor far below residency wastes more than the tail round it avoids
-    return best * 4 >= blocks * 3 ? best : blocks;
-}
-
-void launch_camera(hipStream_t s, int n_cu, const DPathState& st, const DFrame& fr, const DTables& T, const DFilter& f, const DCamera& c, const DSobol& sob, int initial_medium) {
-    const int blocks = cached_blocks<k_camera>(256, n_cu, 8);
-    hipLaunchKernelGGL(k_camera, dim3(clamp_blocks(blocks, st)), dim3(256), 0, s, st, fr, T, f, c, sob, initial_medium);
-}
-void launch_trace(hipStream_t s, int n_cu, const DPathState& st, const DScene& sc, const DTables& T, const DFrame& fr, int depth, DStats* stats) {
-    if (sc.all_opaque && sc.n_media == 0) {
-#define HK_LEAN_LAUNCH(K, C, S, B, NC)                                                                                         \
-    {                                                                                                                          \
-        const int blocks = cached_blocks<K<C, S, B, NC>>(B, n_cu, 8);                                                          \
-        hipLaunchKernelGGL((K<C, S, B, NC>), dim3(clamp_blocks(blocks, st, B / 64)), dim3(B), 0, s, st, sc, depth, stats);     \
-    }
-#define HK_LEAN_LAUNCH_QN(K, C, S, B, NC)   /* the quantised nodes of a deep tree (DScene::qnodes) */                            \
-    {                                                                                                                          \
-        const int blocks = cached_blocks<K<C, S, B, NC, true>>(B, n_cu, 8);                                                    \
-        hipLaunchKernelGGL((K<C, S, B, NC, true>), dim3(clamp_blocks(blocks, st, B / 64)), dim3(B), 0, s, st, sc, depth, stats); \
-    }
-// k_trace_lean over a BVH of depth <= 16: ONE 1024-thread block per CU (the 4 waves per SIMD its registers allow anyway) whose LDS
-// holds the 16 stacks (64 KB) and the top 1536 nodes of the tree (84 KB) — all of the Cornell box, the upper levels of the others.
-// Measured (HK_NODE_CACHE=0 switches it off): trace -11 % in the Cornell box and the sky scene; with the 32-entry stacks of the
-// 10^6-triangle scene 512 nodes are a small part of the visits (+-1 %: no cache there).
-// The any-hit kernel lives on residency (7 waves per SIMD on 16 KB of stacks; the big cache cost it three of them: +3 %), so it
-// gets the cache that FITS beside them.  Round 6 (two-spheres Cornell box, A B | B A): what counts is nodes per WAVE-SLOT — a cache is shared by the
-// waves of its block, so bigger blocks buy more of the tree for the same LDS.  12-wave blocks with the top 560 nodes (48 KB of stacks + 31 KB of
-// nodes, two blocks per CU = 6 waves per SIMD): k_shadow 17.55 -> 16.4 ms per Cornell frame, sky 2.6 -> 2.5.  On the way: 4-wave blocks with
-// 112 nodes (rounds 3-5, seven blocks per CU) 17.55, 176 nodes (six blocks) 17.0, 192 / 240 / 320 nodes (five, five, four blocks) 18.5 / 18.3 /
-// 20.3; 8-wave blocks with 384 nodes 20.2 and 14-wave blocks with 432 nodes 22.5 (one block short of the plan each); 16-wave blocks with the
-// whole tree (four waves per SIMD) 17.0.
-#ifndef HK_SHADOW_NC16
-#define HK_SHADOW_NC16 560
-#endif
-#ifndef HK_SHADOW_BLOCK16   // threads per block of the any-hit kernel over trees <= 16 deep
-#define HK_SHADOW_BLOCK16 768
-#endif
-#ifndef HK_SHADOW_NC32
-#define HK_SHADOW_NC32 0
-#endif
-#ifndef HK_TRACE_NC32
-#define HK_TRACE_NC32 128   // 10^6-triangle scene: trace -1.3 % (256 nodes cost a block per CU: +15 %)
-#endif
-#define HK_LEAN_DISPATCH(K, B16, NC16, NC32)                                     \
-    if (sc.bvh_depth <= 16) {                                                    \
-        if (node_cache_mode() != 0) {                                            \
-            if (fr.count_nodes) HK_LEAN_LAUNCH(K, true, 16, B16, NC16)           \
-            else HK_LEAN_LAUNCH(K, false, 16, B16, NC16)                         \
-        } else {                                                                 \
-            if (fr.count_nodes) HK_LEAN_LAUNCH(K, true, 16, HK_TRACE_BLOCK, 0)   \
-            else HK_LEAN_LAUNCH(K, false, 16, HK_TRACE_BLOCK, 0)                 \
-        }                                                                        \
-    } else if (sc.qnodes != nullptr) {                                           \
-        if (node_cache_mode() != 0) {                                            \
-            if (fr.count_nodes) HK_LEAN_LAUNCH_QN(K, true, HK_LDS_STACK, HK_TRACE_BLOCK, NC32)    \
-            else HK_LEAN_LAUNCH_QN(K, false, HK_LDS_STACK, HK_TRACE_BLOCK, NC32) \
-        } else {   /* HK_NODE_CACHE=0 is honoured for the quantised tree too */ \
-            if (fr.count_nodes) HK_LEAN_LAUNCH_QN(K, true, HK_LDS_STACK, HK_TRACE_BLOCK, 0)   \
-            else HK_LEAN_LAUNCH_QN(K, false, HK_LDS_STACK, HK_TRACE_BLOCK, 0)    \
-        }                                                                        \
-    } else {                                                                     \
-        if (node_cache_mode() != 0) {                                            \
-            if (fr.count_nodes) HK_LEAN_LAUNCH(K, true, HK_LDS_STACK, HK_TRACE_BLOCK, NC32)   \
-            else HK_LEAN_LAUNCH(K, false, HK_LDS_STACK, HK_TRACE_BLOCK, NC32)    \
-        } else {                                                                 \
-            if (fr.count_nodes) HK_LEAN_LAUNCH(K, true, HK_LDS_STACK, HK_TRACE_BLOCK, 0)   \
-            else HK_LEAN_LAUNCH(K, false, HK_LDS_STACK, HK_TRACE_BLOCK, 0)       \
-        }                                                                        \
-    }
-        HK_LEAN_DISPATCH(k_trace_lean, 1024, 1536, HK_TRACE_NC32)
-        return;
-    }
-    const int b0 = cached_blocks<k_trace<false>>(HK_TRACE_BLOCK, n_cu, 8), b1 = cached_blocks<k_trace<true>>(HK_TRACE_BLOCK, n_cu, 8);
-    if (fr.count_nodes)
-        hipLaunchKernelGGL(k_trace<true>, dim3(clamp_blocks(b1, st)), dim3(HK_TRACE_BLOCK), 0, s, st, sc, T, fr, depth, stats);
-    else
-        hipLaunchKernelGGL(k_trace<false>, dim3(clamp_blocks(b0, st)), dim3(HK_TRACE_BLOCK), 0, s, st, sc, T, fr, depth, stats);
-}
-static int grey_mode() {   // HK_GREY=0: flat-spectrum media run through the general tracking kernels (A/B switch, looked up per launch in the context's knob table)
-    const char* e = hk::knob("HK_GREY");
-    return e ? std::atoi(e) : 1;
-}
-static int grey_flat_mode() {   // HK_GREY_FLAT=0: grey media run through the round-3 GREY instantiations of k_track / k_shadow_walk (A/B switch, looked up per launch in the context's knob table)
-    const char* e = hk::knob("HK_GREY_FLAT");
-    return e ? std::atoi(e) : 1;
-}
-static int walk_pool_mode() {   // HK_WALK_POOL=0: k_shadow_walk<.., GREY> instead of k_walk_pool (A/B switch, looked up per launch in the context's knob table)
-    const char* e = hk::knob("HK_WALK_POOL");
-    return e ? std::atoi(e) : 1;
-}
-static int track_pool_mode() {   // HK_TRACK_POOL=0: k_track_flat instead of k_track_pool (A/B switch, looked up per launch in the context's knob table)
-    const char* e = hk::knob("HK_TRACK_POOL");
-    return e ? std::atoi(e) : 1;
-}
-// media kernels are instantiated for a single medium kind or for all four (15)
-static int media_mask_class(const DScene& sc) {
-    int m = sc.media_mask;
-    return (m == 1 || m == 2 || m == 4 || m == 8) ? m : 15;
-}
-static int walk_split_mode() {   // HK_WALK_SPLIT=1: the grey medium's shadow walk runs as k_walk_cast / k_walk_track rounds instead of ONE k_shadow_walk<.., GREY>
-    const char* e = hk::knob("HK_WALK_SPLIT");   // (measured on the BOMEX stand-in: cast rounds 0.085 s + tracking rounds 0.45 s against 0.51 s unsplit — off by default)
-    return e ? std::atoi(e) : 0;
-}
-template <bool C, int MM>
-static void launch_walk_split(hipStream_t s, int n_cu, const DPathState& st, const DScene& sc, const DFrame& fr, int depth, DStats* stats) {
-    const int cb = clamp_blocks(cached_blocks<k_walk_cast<C, MM, 16>>(HK_TRACE_BLOCK, n_cu, 8), st);
-    const int tb = clamp_blocks(cached_blocks<k_walk_track<MM>>(256, n_cu, 8), st);
-    for (int round = 0; round < HK_WALK_ROUNDS; ++round) {
-        hipLaunchKernelGGL((k_walk_cast<C, MM, 16>), dim3(cb), dim3(HK_TRACE_BLOCK), 0, s, st, sc, depth, round, stats, sc.media);
-        hipLaunchKernelGGL((k_walk_track<MM>), dim3(tb), dim3(256), 0, s, st, sc, depth, round, fr.walk_tune, stats, sc.media);
-    }
-}
-// The compact records (r_u == 1 not stored, r_l one float: DPathState::compact) also hold in a scene whose one medium is grey AND runs
-// through the pool kernels (k_track_pool / k_walk_pool, the only media kernels that know the compact layout): r_u is never touched
-// there and every factor of r_l is a scalar.  HK_GREY_COMPACT=0: the full records.
-bool grey_compact_ok(const DScene& sc) {
-    const char* e = hk::knob("HK_GREY_COMPACT");
-    if (e && std::atoi(e) == 0) return false;
-    const int mc = sc.n_media > 0 ? media_mask_class(sc) : 0;
-    return sc.n_media == 1 && sc.all_grey && sc.grey_pool && (mc == 2 || mc == 8) && sc.bvh_depth <= 16 && grey_mode() && grey_flat_mode() && track_pool_mode() && walk_pool_mode() &&
-           !walk_split_mode();
-}
-void launch_shadow(hipStream_t s, int n_cu, const DPathState& st, const DScene& sc, const DTables& T, const DFrame& fr, int depth, DStats* stats) {
-    if (sc.all_opaque && sc.n_media == 0) {
-        HK_LEAN_DISPATCH(k_shadow, HK_SHADOW_BLOCK16, HK_SHADOW_NC16, HK_SHADOW_NC32)
-        return;
-    }
-    if (sc.all_grey && grey_mode() && walk_split_mode() && sc.bvh_depth <= 16 && st.wq_a != nullptr) {
-        const int mc = media_mask_class(sc);
-        if (mc == 8) {
-            if (fr.count_nodes) launch_walk_split<true, 8>(s, n_cu, st, sc, fr, depth, stats); else launch_walk_split<false, 8>(s, n_cu, st, sc, fr, depth, stats);
-            return;
-        }
-        if (mc == 2) {
-            if (fr.count_nodes) launch_walk_split<true, 2>(s, n_cu, st, sc, fr, depth, stats); else launch_walk_split<false, 2>(s, n_cu, st, sc, fr, depth, stats);
-            return;
-        }
-    }
-#define HK_SHADOW_LAUNCH(C, MM)                                                                                                        \
-    if (sc.bvh_depth <= 16 && (MM == 2 || MM == 8) && sc.grey_pool && grey_mode() && grey_flat_mode() && walk_pool_mode()) {         \
-        constexpr int M2 = (MM == 2 || MM == 8) ? MM : 8;                                                                              \
-        if (M2 == 8 && sc.grey_bricks && sc.bvh_depth <= 8 && walk_pool_mode() == 1) {                                                 \
-            const int blocks = cached_blocks<k_walk_pool<C, 8, true, 8, 64>>(HK_TRACE_BLOCK, n_cu, 8);                                 \
-            hipLaunchKernelGGL((k_walk_pool<C, 8, true, 8, 64>), dim3(clamp_blocks(blocks, st)), dim3(HK_TRACE_BLOCK), 0, s, st, sc, depth, fr.walk_tune, fr.track_gate, stats, sc.media); \
-        } else if (M2 == 8 && sc.grey_bricks) {                                                                                        \
-            const int blocks = cached_blocks<k_walk_pool<C, 8, true, 16, 56>>(HK_TRACE_BLOCK, n_cu, 8);                                \
-            hipLaunchKernelGGL((k_walk_pool<C, 8, true, 16, 56>), dim3(clamp_blocks(blocks, st)), dim3(HK_TRACE_BLOCK), 0, s, st, sc, depth, fr.walk_tune, fr.track_gate, stats, sc.media); \
-        } else {                                                                                                                       \
-            const int blocks = cached_blocks<k_walk_pool<C, M2, false, 16, 56>>(HK_TRACE_BLOCK, n_cu, 8);                              \
-            hipLaunchKernelGGL((k_walk_pool<C, M2, false, 16, 56>), dim3(clamp_blocks(blocks, st)), dim3(HK_TRACE_BLOCK), 0, s, st, sc, depth, fr.walk_tune, fr.track_gate, stats, sc.media); \
-        }                                                                                                                              \
-    } else if (sc.bvh_depth <= 16 && (MM == 2 || MM == 8) && sc.all_grey && grey_mode()) {                                           \
-        constexpr int M2 = (MM == 2 || MM == 8) ? MM : 8;                                                                              \
-        const int blocks = cached_blocks<k_shadow_walk<C, M2, 16, true>>(HK_TRACE_BLOCK, n_cu, 8);                                   \
-        hipLaunchKernelGGL((k_shadow_walk<C, M2, 16, true>), dim3(clamp_blocks(blocks, st)), dim3(HK_TRACE_BLOCK), 0, s, st, sc, T, depth, fr.walk_tune, stats, sc.media); \
-    } else if (sc.bvh_depth <= 16) {   /* 16-entry stacks: 16 KB per block */                                                       \
-        const int blocks = cached_blocks<k_shadow_walk<C, MM, 16>>(HK_TRACE_BLOCK, n_cu, 8);                                         \
-        hipLaunchKernelGGL((k_shadow_walk<C, MM, 16>), dim3(clamp_blocks(blocks, st)), dim3(HK_TRACE_BLOCK), 0, s, st, sc, T, depth, fr.walk_tune, stats, sc.media); \
-    } else {                                                                                                                           \
-        const int blocks = cached_blocks<k_shadow_walk<C, MM>>(HK_TRACE_BLOCK, n_cu, 8);                                             \
-        hipLaunchKernelGGL((k_shadow_walk<C, MM>), dim3(clamp_blocks(blocks, st)), dim3(HK_TRACE_BLOCK), 0, s, st, sc, T, depth, fr.walk_tune, stats, sc.media); \
-    }
-#define HK_SHADOW_MM(C)                                   \
-    switch (sc.n_media > 0 ? media_mask_class(sc) : 0) {  \
-        case 0: HK_SHADOW_LAUNCH(C, 0) break;             \
-        case 1: HK_SHADOW_LAUNCH(C, 1) break;             \
-        case 2: HK_SHADOW_LAUNCH(C, 2) break;             \
-        case 4: HK_SHADOW_LAUNCH(C, 4) break;             \
-        case 8: HK_SHADOW_LAUNCH(C, 8) break;             \
-        default: HK_SHADOW_LAUNCH(C, 15) break;           \
-    }
-    if (fr.count_nodes) {
-        HK_SHADOW_MM(true)
-    } else {
-        HK_SHADOW_MM(false)
-    }
-#undef HK_SHADOW_MM
-#undef HK_SHADOW_LAUNCH
-}
-// work lists of up to HK_MAX_KINDS + 6 queues (pairs depth, queue id) in one launch
-void launch_segment_lists(hipStream_t s, const DPathState& st, int n, const int* depths, const int* queues) {
-    if (n <= 0) return;
-    SegQueues qs;
-    qs.n = n;
-    for (int i = 0; i < n; ++i) {
-        qs.depth[i] = depths[i];
-        qs.q[i] = queues[i];
-    }
-    hipLaunchKernelGGL(k_segment_lists, dim3(n, HK_LIST_SPLIT), dim3(1024), 0, s, st, qs);
-}
-void launch_medium(hipStream_t s, int n_cu, const DPathState& st, const DScene& sc, const DTables& T, const DFrame& fr, const DSobol& sob, int depth, DStats* stats) {
-    {
-        const int d = depth, q = Q_MEDIUM;
-        launch_segment_lists(s, st, 1, &d, &q);
-    }
-#define COMMA ,
-#define HK_TRACK_LAUNCH(MM)                                                                                              \
-    {                                                                                                                    \
-        const int blocks = cached_blocks<k_track<MM>>(256, n_cu, 8);                                                   \
-        hipLaunchKernelGGL((k_track<MM>), dim3(clamp_blocks(blocks, st)), dim3(256), 0, s, st, sc, T, fr, depth, stats, sc.media);   \
-    }
-#define HK_TRACK_FLAT(MM, B)                                                                                             \
-    if (pool) {                                                                                                          \
-        const int blocks = cached_blocks<k_track_pool<MM, B>>(256, n_cu, 8);                                           \
-        hipLaunchKernelGGL((k_track_pool<MM, B>), dim3(clamp_blocks(blocks, st)), dim3(256), 0, s, st, sc, fr, depth, stats, sc.media);   \
-    } else {                                                                                                             \
-        const int blocks = cached_blocks<k_track_flat<MM, B>>(256, n_cu, 8);                                           \
-        hipLaunchKernelGGL((k_track_flat<MM, B>), dim3(clamp_blocks(blocks, st)), dim3(256), 0, s, st, sc, fr, depth, stats, sc.media);   \
-    }
-    const bool grey = sc.all_grey && grey_mode();
-    const bool flat = grey && grey_flat_mode();
-    const bool pool = flat && track_pool_mode() && sc.grey_pool;
-    switch (media_mask_class(sc)) {
-        case 1: HK_TRACK_LAUNCH(1) break;
-        case 2: if (flat) HK_TRACK_FLAT(2, false) else if (grey) HK_TRACK_LAUNCH(2 COMMA true) else HK_TRACK_LAUNCH(2) break;
-        case 4: HK_TRACK_LAUNCH(4) break;
-        case 8: if (flat && sc.grey_bricks) HK_TRACK_FLAT(8, true) else if (flat) HK_TRACK_FLAT(8, false) else if (grey) HK_TRACK_LAUNCH(8 COMMA true) else HK_TRACK_LAUNCH(8) break;
-        default: HK_TRACK_LAUNCH(15) break;
-    }
-#undef HK_TRACK_LAUNCH
-#undef HK_TRACK_FLAT
-    {
-        const int d = depth, q = Q_SCATTER;
-        launch_segment_lists(s, st, 1, &d, &q);
-    }
-    const char* ft_env = hk::knob("HK_SOBOL_TABLE_ONLY");   // looked up per launch in the context's knob table (A/B switch)
-    if (sob.hi_table != nullptr && sob.lo_table != nullptr && 9 + 5 * depth < sob.lo_rows && 9 + 5 * depth < sob.hi_rows && !(ft_env && std::atoi(ft_env) == 0)) {
-        const int sblocks = cached_blocks<k_scatter<true>>(256, n_cu, 8);
-        hipLaunchKernelGGL(k_scatter<true>, dim3(clamp_blocks(sblocks, st)), dim3(256), 0, s, st, sc, T, fr, sob, depth, stats);
-    } else {
-        const int sblocks = cached_blocks<k_scatter<false>>(256, n_cu, 8);
-        hipLaunchKernelGGL(k_scatter<false>, dim3(clamp_blocks(sblocks, st)), dim3(256), 0, s, st, sc, T, fr, sob, depth, stats);
-    }
-}
-void launch_detect_camera_medium(hipStream_t s, const DPathState& st, const DScene& sc, float x, float y, float z, DStats* stats) {
-    hipLaunchKernelGGL(k_detect_camera_medium, dim3(1), dim3(64), 0, s, st, sc, x, y, z, stats);
-}
-void launch_escaped(hipStream_t s, int n_cu, const DPathState& st, const DScene& sc, const DTables& T, const DFrame& fr, int depth) {
-    const char* e = hk::knob("HK_ESCAPED_UNROLL");   // 2: two queue entries per lane and iteration (A/B switch; films bit-identical).  Measured, sky: 8.9 ->
-    if (!(e && std::atoi(e) == 2)) {                  // 10.4 ms per frame — its registers cost the kernel a block per CU (3 instead of 4); off
-        const int blocks = cached_blocks<k_escaped<1>>(256, n_cu, 8);
-        hipLaunchKernelGGL(k_escaped<1>, dim3(clamp_blocks(blocks, st)), dim3(256), 0, s, st, sc, T, depth, fr.implicit_ones);   // (one wave per segment instead of the resident stride: +-0, sky)
-    } else {
-        const int blocks = cached_blocks<k_escaped<2>>(256, n_cu, 8);
-        hipLaunchKernelGGL(k_escaped<2>, dim3(clamp_blocks(blocks, st)), dim3(256), 0, s, st, sc, T, depth, fr.implicit_ones);
-    }
-}
-static bool sobol_tables_cover(const DSobol& sob, int depth) {
-    const char* ft_env = hk::knob("HK_SOBOL_TABLE_ONLY");   // looked up per launch in the context's knob table (A/B switch)
-    return sob.hi_table != nullptr && sob.lo_table != nullptr && 9 + 5 * depth < sob.lo_rows && 9 + 5 * depth < sob.hi_rows && !(ft_env && std::atoi(ft_env) == 0);
-}
-// scenes whose next-event light is chosen by k_light_select before the shade kernels run (HK_PRESELECT=0: never)
-bool preselect_lights(const DScene& sc, const DPathState& st) {
-    const char* e = hk::knob("HK_PRESELECT");
-    return sc.n_media == 0 && sc.num_bvh_lights >= HK_PRESELECT_MIN && st.sel_light != nullptr && !(e && std::atoi(e) == 0);
-}
-void launch_light_select(hipStream_t s, int n_cu, const DPathState& st, const DScene& sc, const DTables& T, const DFrame& fr, const DSobol& sob, int depth, uint32_t kinds_mask, DStats* stats) {
-    int min_idle = HK_SELECT_MIN_IDLE;
-    if (const char* e = hk::knob("HK_SELECT_MIN_IDLE")) min_idle = std::atoi(e) >= 1 && std::atoi(e) <= 64 ? std::atoi(e) : min_idle;
-    const char* pe = hk::knob("HK_SELECT_POOL");   // 0: the per-lane-refill kernel of round 4 (A/B switch; films bit-identical)
-    if (!(pe && std::atoi(pe) == 0)) {
-        if (sobol_tables_cover(sob, depth)) {
-            const int blocks = cached_blocks<k_light_select_pool<true>>(HK_SELECT_BLOCK, n_cu, 8);
-            hipLaunchKernelGGL(k_light_select_pool<true>, dim3(clamp_blocks(blocks, st, HK_SELECT_BLOCK / 64)), dim3(HK_SELECT_BLOCK), 0, s, st, sc, T, fr, sob, depth, kinds_mask, stats);
-        } else {
-            const int blocks = cached_blocks<k_light_select_pool<false>>(HK_SELECT_BLOCK, n_cu, 8);
-            hipLaunchKernelGGL(k_light_select_pool<false>, dim3(clamp_blocks(blocks, st, HK_SELECT_BLOCK / 64)), dim3(HK_SELECT_BLOCK), 0, s, st, sc, T, fr, sob, depth, kinds_mask, stats);
-        }
-        return;
-    }
-    if (sobol_tables_cover(sob, depth)) {
-        const int blocks = cached_blocks<k_light_select<true>>(256, n_cu, 8);
-        hipLaunchKernelGGL(k_light_select<true>, dim3(clamp_blocks(blocks, st)), dim3(256), 0, s, st, sc, T, fr, sob, depth, kinds_mask, min_idle, stats);
-    } else {
-        const int blocks = cached_blocks<k_light_select<false>>(256, n_cu, 8);
-        hipLaunchKernelGGL(k_light_select<false>, dim3(clamp_blocks(blocks, st)), dim3(256), 0, s, st, sc, T, fr, sob, depth, kinds_mask, min_idle, stats);
-    }
-}
-void launch_shade(hipStream_t s, int n_cu, int kind, const DPathState& st, const DScene& sc, const DTables& T, const DFrame& fr, const DSobol& sob, int depth, int first_kind, DStats* stats) {
-#define HK_SHADE_CASE(K)                                                                                                          \
-    case K: {                                                                                                                     \
-        const int blocks = cached_blocks<k_shade<K>>(256, n_cu, 8);                                                            \
-        hipLaunchKernelGGL(k_shade<K>, dim3(clamp_blocks(blocks, st)), dim3(256), 0, s, st, sc, T, fr, sob, depth, first_kind, stats); \
-    } break;
-    // both sampler tables hold every draw of this bounce (rows up to 9 + 5 depth: sobol_row) for every path of the pass: the table-only
-    // instantiation (HK_SOBOL_TABLE_ONLY=0: always the general one — A/B switch, looked up per launch in the context's knob table)
-    const bool ft = sobol_tables_cover(sob, depth);
-    if (preselect_lights(sc, st)) {   // k_light_select has run for this depth: the instantiations without the light-BVH descent
-#define HK_SHADE_PRE(K)                                                                                                                 \
-    if (kind == K) {                                                                                                                    \
-        if (ft) {                                                                                                                       \
-            const int blocks = cached_blocks<k_shade<K, false, true, true>>(256, n_cu, 8);                                            \
-            hipLaunchKernelGGL((k_shade<K, false, true, true>), dim3(clamp_blocks(blocks, st)), dim3(256), 0, s, st, sc, T, fr, sob, depth, first_kind, stats); \
-        } else {                                                                                                                        \
-            const int blocks = cached_blocks<k_shade<K, false, false, true>>(256, n_cu, 8);                                           \
-            hipLaunchKernelGGL((k_shade<K, false, false, true>), dim3(clamp_blocks(blocks, st)), dim3(256), 0, s, st, sc, T, fr, sob, depth, first_kind, stats); \
-        }                                                                                                                               \
-        return;                                                                                                                         \
-    }
-        HK_SHADE_PRE(HK_MAT_MATTE)
-        HK_SHADE_PRE(HK_MAT_MIRROR)
-        HK_SHADE_PRE(HK_MAT_GLASS)
-        HK_SHADE_PRE(HK_MAT_CONDUCTOR)
-#undef HK_SHADE_PRE
-    }
-    if (kind == HK_MAT_MATTE && sc.simple_lights) {
-        if (ft) {
-            const int blocks = cached_blocks<k_shade<HK_MAT_MATTE, true, true>>(256, n_cu, 8);
-            hipLaunchKernelGGL((k_shade<HK_MAT_MATTE, true, true>), dim3(clamp_blocks(blocks, st)), dim3(256), 0, s, st, sc, T, fr, sob, depth, first_kind, stats);
-        } else {
-            const int blocks = cached_blocks<k_shade<HK_MAT_MATTE, true>>(256, n_cu, 8);
-            hipLaunchKernelGGL((k_shade<HK_MAT_MATTE, true>), dim3(clamp_blocks(blocks, st)), dim3(256), 0, s, st, sc, T, fr, sob, depth, first_kind, stats);
-        }
-        return;
-    }
-#define HK_SHADE_FT(K)                                                                                                                  \
-    if (kind == K && ft) {                                                                                                              \
-        const int blocks = cached_blocks<k_shade<K, false, true>>(256, n_cu, 8);                                                      \
-        hipLaunchKernelGGL((k_shade<K, false, true>), dim3(clamp_blocks(blocks, st)), dim3(256), 0, s, st, sc, T, fr, sob, depth, first_kind, stats); \
-        return;                                                                                                                         \
-    }
-    HK_SHADE_FT(HK_MAT_MATTE)
-    HK_SHADE_FT(HK_MAT_MIRROR)
-    HK_SHADE_FT(HK_MAT_GLASS)
-    HK_SHADE_FT(HK_MAT_CONDUCTOR)
-#undef HK_SHADE_FT
-    switch (kind) {
-        HK_SHADE_CASE(HK_MAT_MATTE)
-        HK_SHADE_CASE(HK_MAT_MIRROR)
-        HK_SHADE_CASE(HK_MAT_GLASS)
-        HK_SHADE_CASE(HK_MAT_CONDUCTOR)
-        HK_SHADE_CASE(HK_MAT_COATED_DIFFUSE)
-        HK_SHADE_CASE(HK_MAT_THIN_DIELECTRIC)
-        HK_SHADE_CASE(HK_MAT_DIFFUSE_TRANSMISSION)
-        HK_SHADE_CASE(HK_MAT_COATED_DIFFUSE_TRANSMISSION)
-        HK_SHADE_CASE(HK_MAT_COATED_CONDUCTOR)
-        default: {
-            const int blocks = cached_blocks<k_shade<HK_MAT_FALLBACK>>(256, n_cu, 8);
-            hipLaunchKernelGGL(k_shade<HK_MAT_FALLBACK>, dim3(clamp_blocks(blocks, st)), dim3(256), 0, s, st, sc, T, fr, sob, depth, first_kind, stats);
-        } break;
-    }
-#undef HK_SHADE_CASE
-}
-// k_small_pass: the whole pass of a small call in one launch.  -> false when this scene / pass is not its case (the caller launches the stages)
-#ifndef HK_SMALL_PASS_NC
-#define HK_SMALL_PASS_NC 1536
-#endif
-// the scenes k_small_pass is instantiated for (the pass itself must be a small one: launch_small_pass): -> 0 none, 1 the all-matte closed
-// scene under simple lights, 2 the general instantiation (Matte / Mirror / Glass / Conductor, escape lights)
-static int small_pass_class(const DScene& sc, uint32_t kinds_mask) {
-    const char* e = hk::knob("HK_SMALL_PASS_FUSED");   // 0: the stages as launches, 1: only the all-matte instantiation (A/B switch; films bit-identical)
-    const int mode = e ? std::atoi(e) : 2;
-    if (mode == 0) return 0;
-    if (!(sc.all_opaque && sc.n_media == 0 && sc.bvh_depth <= HK_LDS_STACK && node_cache_mode() != 0)) return 0;
-    if (kinds_mask == (1u << HK_MAT_MATTE) && sc.simple_lights && !sc.has_escape_lights && sc.bvh_depth <= 16 && sc.num_bvh_lights < HK_PRESELECT_MIN) return 1;
-    const uint32_t light_kinds = (1u << HK_MAT_MATTE) | (1u << HK_MAT_MIRROR) | (1u << HK_MAT_GLASS) | (1u << HK_MAT_CONDUCTOR);
-    return (mode >= 2 && kinds_mask != 0 && (kinds_mask & ~light_kinds) == 0) ? 2 : 0;
-}
-bool small_pass_fusable(const DScene& sc, uint32_t kinds_mask) { return small_pass_class(sc, kinds_mask) != 0; }
-bool launch_small_pass(hipStream_t s, int n_cu, const DPathState& st, const DScene& sc, const DTables& T, const DFrame& fr, const DFilter& flt, const DCamera& cam, const DSobol& sob, int max_depth,
-                       uint32_t kinds_mask, DStats* stats, bool dry, void* accum, int film_mode) {   // dry: only say whether this pass would be launched; film_mode: 0 the caller launches k_film, 1 / 2: float / double accumulators, added inside (one-sample passes)
-    const int cls = small_pass_class(sc, kinds_mask);
-    if (cls == 0 || !st.small_pass || st.dynamic_segments || fr.count_nodes) return false;
-    // a SMALL pass in ensure_state's sense (at most 16 chunks for each of 4 waves per CU), not the mid-size pass that shares its static
-    // segments: with 25 chunks per stage the launches' higher residency wins (800^2 x 32 spp without sampler tables: 14.8 ms as launches, 17.2 here)
-    if (((long)st.capacity + 63) / 64 / 16 > 4L * n_cu) return false;
-    for (int depth = 0; depth < max_depth; ++depth)
-        if (sobol_tables_cover(sob, depth)) return false;
-    // one block per CU (its LDS: 16-entry stacks, the top of the tree, the emission lists) of as many waves as the pass has segments per CU
-    const char* me = hk::knob("HK_SMALL_PASS_MERGED");   // 0: shadow rays and the next bounce's rays as two stages (A/B switch; films bit-identical)
-    const int merged = (me && std::atoi(me) == 0) ? 0 : 1;
-#define HK_SMALL_PASS_LAUNCH(B, G, ...)                                                                                                                     \
-    {                                                                                                                                                       \
-        int blocks = cached_blocks<k_small_pass<HK_SMALL_PASS_NC, B, G, ##__VA_ARGS__>>(B, n_cu, 1);                                                        \
-        if (blocks * (B / 64) > st.n_waves) blocks = st.n_waves / (B / 64);                                                                                 \
-        if (blocks < 1) return false;                                                                                                                       \
-        if (!dry) hipLaunchKernelGGL((k_small_pass<HK_SMALL_PASS_NC, B, G, ##__VA_ARGS__>), dim3(blocks), dim3(B), 0, s, st, sc, T, fr, flt, cam, sob, max_depth, sc.n_lights > 0 ? 1 : 0, merged, accum, film_mode, kinds_mask, stats); \
-    }
-    // (Cornell 800^2, one sample per call: 1.42 / 1.05 / 1.14 ms at 4 / 8 / 16 segments per CU — 256- / 512- / 1024-thread blocks; a 768-thread
-    // block for 12: 1.55.  Eight waves per CU hold 312 paths each: chunks stay fuller down the bounces than with 156, and at two waves per
-    // SIMD nothing spills.)
-    // two waves per SIMD at most: at 16 segments per CU (1 024-thread blocks, 128 registers) the matte instantiation spilled 372 B per lane
-    // and lost to 8 (1.14 ms against 1.05), the general one does not fit at all — such a pass keeps the launches
-    if (st.n_waves > 8 * n_cu) return false;
-    if (cls == 2) {
-        if (sc.bvh_depth > 16) {
-            if (st.n_waves > 4 * n_cu) HK_SMALL_PASS_LAUNCH(512, true, HK_LDS_STACK)
-            else HK_SMALL_PASS_LAUNCH(256, true, HK_LDS_STACK)
-        } else if (st.n_waves > 4 * n_cu) HK_SMALL_PASS_LAUNCH(512, true)
-        else HK_SMALL_PASS_LAUNCH(256, true)
-        return true;
-    }
-    if (st.n_waves > 4 * n_cu) HK_SMALL_PASS_LAUNCH(512, false)
-    else HK_SMALL_PASS_LAUNCH(256, false)
-#undef HK_SMALL_PASS_LAUNCH
-    return true;
-}
-void launch_film(hipStream_t s, const DPathState& st, const DFrame& fr, const DTables& T, void* accum, bool f64) {
-    int g = grid_for(fr.n_pixels_padded >> 6, 4, 4096);   // one wave per 8x8 tile
-    if (f64)
-        hipLaunchKernelGGL(k_film<double>, dim3(g), dim3(256), 0, s, st, fr, T, (double*)accum);
-    else
-        hipLaunchKernelGGL(k_film<float>, dim3(g), dim3(256), 0, s, st, fr, T, (float*)accum);
-}
-void launch_finalize(hipStream_t s, const void* accum, bool f64, float* out, int w, int h) {
-    int g = grid_for(w * h, 256, 4096);
-    if (f64)
-        hipLaunchKernelGGL(k_finalize<double>, dim3(g), dim3(256), 0, s, (const double*)accum, out, w, h);
-    else
-        hipLaunchKernelGGL(k_finalize<float>, dim3(g), dim3(256), 0, s, (const float*)accum, out, w, h);
-}
-template <int KIND>
-__device__ void test_bsdf_one(const DScene& sc, const DTables& T, const DMaterial& m, int mode, bool regularize, v3 wo, v3 wi, v3 ns, S4 lambda, v2 u, float uc, float* r) {
-    if (mode == 0) {
-        BSDFSample b = sample_bsdf<KIND>(sc, T, m, wo, ns, mk2(0.0f, 0.0f), lambda, u, uc, regularize);
-        r[0] = b.wi.x, r[1] = b.wi.y, r[2] = b.wi.z;
-        r[3] = b.f.x, r[4] = b.f.y, r[5] = b.f.z, r[6] = b.f.w;
-        r[7] = b.pdf, r[8] = b.is_specular ? 1.0f : 0.0f, r[9] = b.eta_scale;
-    } else {
-        float pdf;
-        S4 f = eval_bsdf<KIND>(sc, T, m, wo, wi, ns, mk2(0.0f, 0.0f), lambda, pdf);
-        r[0] = f.x, r[1] = f.y, r[2] = f.z, r[3] = f.w, r[4] = pdf;
-        r[5] = r[6] = r[7] = r[8] = r[9] = 0.0f;
-    }
-}
-__global__ void k_test_bsdf(DScene sc, DTables T, int mode, int mat_idx, int regularize, int n, const float* wo, const float* wi, const float* ns, const float* lambda,
-                            const float* u, const float* uc, float* out) {
-    const DMaterial& m = sc.materials[mat_idx];
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    v3 o = mk3(wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]), d = mk3(wi[3 * i], wi[3 * i + 1], wi[3 * i + 2]), nn = mk3(ns[3 * i], ns[3 * i + 1], ns[3 * i + 2]);
-    S4 l = s4(lambda[4 * i], lambda[4 * i + 1], lambda[4 * i + 2], lambda[4 * i + 3]);
-    v2 uu = mk2(u[2 * i], u[2 * i + 1]);
-    float* r = out + 10 * (size_t)i;
-#define HK_TB_CASE(K) \
-    case K: test_bsdf_one<K>(sc, T, m, mode, regularize != 0, o, d, nn, l, uu, uc[i], r); break;
-    switch (m.kind) {
-        HK_TB_CASE(HK_MAT_MATTE)
-        HK_TB_CASE(HK_MAT_MIRROR)
-        HK_TB_CASE(HK_MAT_GLASS)
-        HK_TB_CASE(HK_MAT_CONDUCTOR)
-        HK_TB_CASE(HK_MAT_COATED_DIFFUSE)
-        HK_TB_CASE(HK_MAT_THIN_DIELECTRIC)
-        HK_TB_CASE(HK_MAT_DIFFUSE_TRANSMISSION)
-        HK_TB_CASE(HK_MAT_COATED_DIFFUSE_TRANSMISSION)
-        HK_TB_CASE(HK_MAT_COATED_CONDUCTOR)
-        default: test_bsdf_one<HK_MAT_FALLBACK>(sc, T, m, mode, regularize != 0, o, d, nn, l, uu, uc[i], r); break;
-    }
-    }
-#undef HK_TB_CASE
-}
-__global__ void k_test_light(DScene sc, DTables T, int mode, int light_idx, int n, const float* p3, const float* in3, const float* lambda, float* out) {
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        S4 l = s4(lambda[4 * i], lambda[4 * i + 1], lambda[4 * i + 2], lambda[4 * i + 3]);
-        v3 a = mk3(in3[3 * i], in3[3 * i + 1], in3[3 * i + 2]);
-        float* r = out + 12 * (size_t)i;
-        for (int k = 0; k < 12; ++k) r[k] = 0.0f;
-        if (mode == 0) {
-            LightSample ls = sample_light(sc, T, sc.lights[light_idx - 1], mk3(p3[3 * i], p3[3 * i + 1], p3[3 * i + 2]), l, mk2(a.x, a.y));
-            r[0] = ls.wi.x, r[1] = ls.wi.y, r[2] = ls.wi.z, r[3] = ls.pdf;
-            r[4] = ls.Li.x, r[5] = ls.Li.y, r[6] = ls.Li.z, r[7] = ls.Li.w;
-            r[8] = ls.p_light.x, r[9] = ls.p_light.y, r[10] = ls.p_light.z, r[11] = ls.is_delta ? 1.0f : 0.0f;
-        } else {
-            S4 Le = s4(0.0f);
-            float pdf = 0.0f;
-            for (int li = 0; li < sc.n_lights; ++li) {
-                const DLight& L = sc.lights[li];
-                if (L.kind == HK_LIGHT_AMBIENT) Le = Le + L.scale * light_spectrum(L, l);
-                if (L.kind == HK_LIGHT_ENVIRONMENT) {
-                    float4 t = env_eval(sc.envmaps[L.Le_tex], a);
-                    Le = Le + eval_illuminant(coef_illuminant(T, t.x * L.Le_rgba[0], t.y * L.Le_rgba[1], t.z * L.Le_rgba[2]), l);
-                    pdf = pdf + env_pdf_li(sc.envmaps[L.Le_tex], a);
-                }
-            }
-            r[0] = Le.x, r[1] = Le.y, r[2] = Le.z, r[3] = Le.w, r[4] = pdf;
-        }
-    }
-}
-void launch_test_mix(hipStream_t s, const DScene& sc, int mat_idx, int n, const float* p3, const float* wo3, const float* uv2, int* out) {
-    hipLaunchKernelGGL(k_test_mix, dim3(grid_for(n, 256, 1024)), dim3(256), 0, s, sc, mat_idx, n, p3, wo3, uv2, out);
-}
-void launch_test_medium(hipStream_t s, const DScene& sc, const DTables& T, int mode, int medium_idx, int n, const float* a3, const float* b3, const float* tmax, const float* lambda,
-                        float* out) {
-#define HK_TM_LAUNCH(MM) hipLaunchKernelGGL((k_test_medium<MM>), dim3(grid_for(n, 64, 4096)), dim3(64), 0, s, sc, T, mode, medium_idx, n, a3, b3, tmax, lambda, out)
-    switch (media_mask_class(sc)) {
-        case 1: HK_TM_LAUNCH(1); break;
-        case 2: HK_TM_LAUNCH(2); break;
-        case 4: HK_TM_LAUNCH(4); break;
-        case 8: HK_TM_LAUNCH(8); break;
-        default: HK_TM_LAUNCH(15); break;
-    }
-#undef HK_TM_LAUNCH
-}
-int test_majorant_stride() { return 1 + 3 * HK_TEST_MAJ_SEGS; }
-void launch_test_trace_lean(hipStream_t s, int n_cu, const DScene& sc, int anyhit, int n, const float* o, const float* d, const float* tmax, float* t, int* prim, float* uv) {
-    const int blocks = n_cu * 2;
-#define HK_TL_LAUNCH(A, S) hipLaunchKernelGGL((k_test_trace_lean<A, S>), dim3(blocks), dim3(HK_TRACE_BLOCK), 0, s, sc, n, o, d, tmax, t, prim, uv)
-    if (sc.bvh_depth <= 16) {
-        if (anyhit) HK_TL_LAUNCH(true, 16); else HK_TL_LAUNCH(false, 16);
-    } else if (sc.qnodes != nullptr) {   // the kernels' own choice for a deep tree: its quantised nodes
-        if (anyhit) hipLaunchKernelGGL((k_test_trace_lean<true, HK_LDS_STACK, true>), dim3(blocks), dim3(HK_TRACE_BLOCK), 0, s, sc, n, o, d, tmax, t, prim, uv);
-        else hipLaunchKernelGGL((k_test_trace_lean<false, HK_LDS_STACK, true>), dim3(blocks), dim3(HK_TRACE_BLOCK), 0, s, sc, n, o, d, tmax, t, prim, uv);
-    } else {
-        if (anyhit) HK_TL_LAUNCH(true, HK_LDS_STACK); else HK_TL_LAUNCH(false, HK_LDS_STACK);
-    }
-#undef HK_TL_LAUNCH
-}
-void launch_test_trace(hipStream_t s, const DScene& sc, int n, const float* o, const float* d, const float* tmax, float* t, int* prim, float* uv) {
-    hipLaunchKernelGGL(k_test_trace, dim3(grid_for(n, HK_TRACE_BLOCK, 1280)), dim3(HK_TRACE_BLOCK), 0, s, sc, n, o, d, tmax, t, prim, uv);
-}
-void launch_test_sobol(hipStream_t s, const DTables& T, const DSobol& sob, int n, const int* px, const int* py, const int* si, const int* dim, float* o1, float* o2) {
-    hipLaunchKernelGGL(k_test_sobol, dim3(grid_for(n, 256, 1024)), dim3(256), 0, s, T, sob, n, px, py, si, dim, o1, o2);
-}
-void launch_test_camera(hipStream_t s, const DTables& T, const DFilter& f, const DCamera& c, const DSobol& sob, int height, int n, const int* px, const int* py, const int* si,
-                        float* out) {
-    hipLaunchKernelGGL(k_test_camera, dim3(grid_for(n, 256, 1024)), dim3(256), 0, s, T, f, c, sob, height, n, px, py, si, out);
-}
-void launch_test_uplift(hipStream_t s, const DTables& T, int mode, int n, const float* rgb, const float* lam, float* out) {
-    hipLaunchKernelGGL(k_test_uplift, dim3(grid_for(n, 256, 1024)), dim3(256), 0, s, T, mode, n, rgb, lam, out);
-}
-void launch_test_light_bvh(hipStream_t s, const DScene& sc, int n, const float* p, const float* nn, const float* u, int* ol, float* op, const int* q, float* oq) {
-    hipLaunchKernelGGL(k_test_light_bvh, dim3(grid_for(n, 256, 1024)), dim3(256), 0, s, sc, n, p, nn, u, ol, op, q, oq);
-}
-void launch_test_bsdf(hipStream_t s, const DScene& sc, const DTables& T, int mode, int mat_idx, int regularize, int n, const float* wo, const float* wi, const float* ns,
-                      const float* lambda, const float* u, const float* uc, float* out) {
-    hipLaunchKernelGGL(k_test_bsdf, dim3(grid_for(n, 64, 4096)), dim3(64), 0, s, sc, T, mode, mat_idx, regularize, n, wo, wi, ns, lambda, u, uc, out);
-}
-void launch_test_light(hipStream_t s, const DScene& sc, const DTables& T, int mode, int light_idx, int n, const float* p3, const float* in3, const float* lambda, float* out) {
-    hipLaunchKernelGGL(k_test_light, dim3(grid_for(n, 64, 4096)), dim3(64), 0, s, sc, T, mode, light_idx, n, p3, in3, lambda, out);
-}
-void launch_sobol_table(hipStream_t s, const DSobol& sob, const DFrame& fr, uint2* table, int rows) {
-    hipLaunchKernelGGL(k_sobol_table, dim3(grid_for((long)rows * fr.n_pixels_padded > 0x3fffffff ? 0x3fffffff : rows * fr.n_pixels_padded, 256, 8192)), dim3(256), 0, s, sob, fr, table, rows);
-}
-void launch_sobol_lo_table(hipStream_t s, const DSobol& sob, const DFrame& fr, uint16_t* table, int rows, int base, int stride, int count) {
-    hipLaunchKernelGGL(k_sobol_lo_table, dim3(65536), dim3(256), 0, s, sob, fr, table, rows, base, stride, count);
-}
-void launch_postprocess(hipStream_t s, const hk_postprocess_params& P, const float* src, const float* depth, float* dst, int h, int w) {
-    hipLaunchKernelGGL(k_postprocess, dim3(grid_for(h * w, 256, 8192)), dim3(256), 0, s, P, src, depth, dst, h, w);
-}
-void launch_denoise_variance(hipStream_t s, const float* src, float* variance, int h, int w) {
-    hipLaunchKernelGGL(k_denoise_variance, dim3(grid_for(h * w, 256, 8192)), dim3(256), 0, s, src, variance, h, w);
-}
-void launch_denoise_atrous(hipStream_t s, const hk_denoise_params& P, int step, const float* src, const float* normal, const float* depth, const float* variance,
-                           float* dst, int h, int w) {
-    hipLaunchKernelGGL(k_denoise_atrous, dim3(grid_for(h * w, 256, 8192)), dim3(256), 0, s, P, step, src, normal, depth, variance, dst, h, w);
-}
-void launch_slot_of_prim(hipStream_t s, const float4* leaf, int n, int* slot_of_prim) {
-    hipLaunchKernelGGL(k_slot_of_prim, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, leaf, n, slot_of_prim);
-}
-void launch_xform_tris(hipStream_t s, const DXform& X, int first, int n, const float* bp, const float* bn, const float* bt, const int* slot_of_prim, float* pos, float* nrm,
-                       float* tan, float* shade, float4* leaf) {
-    hipLaunchKernelGGL(k_xform_tris, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, X, first, n, bp, bn, bt, slot_of_prim, pos, nrm, tan, shade, leaf);
-}
-void launch_refit_level(hipStream_t s, int begin, int end, DNode* nodes, DQNode* qnodes, const DQGrid& grid, const float4* leaf, const float* pos) {
-    hipLaunchKernelGGL(k_refit_level, dim3(grid_for(end - begin, 256, 8192)), dim3(256), 0, s, begin, end, nodes, qnodes, grid, leaf, pos);
-}
-void launch_aux(hipStream_t s, const DScene& sc, const DCamera& cam, int h, int w, float miss_depth, float* albedo, float* normal, float* depth) {
-    hipLaunchKernelGGL(k_aux, dim3(grid_for(h * w, HK_TRACE_BLOCK, 2048)), dim3(HK_TRACE_BLOCK), 0, s, sc, cam, h, w, miss_depth, albedo, normal, depth);
-}
-
-}  // namespace hk
+#include "hk_launch_impl.h"
+#include "hk_test_kernels.h"

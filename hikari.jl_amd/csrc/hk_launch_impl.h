@@ -1,0 +1,403 @@
+// hk_launch_impl.h — the launch layer (hk_launch.h): part of the hk_kernels.hip translation unit, included after the kernels.
+// Every resident-grid launch goes through launch_resident; a run-time bool or small integer class that selects a template argument goes
+// through with_bool / with_int.  A new kernel instantiation is one more call of those — the compiler checks its arguments.
+#pragma once
+#include "hk_launch.h"
+
+namespace hk {
+
+template <bool V>
+using bool_c = std::bool_constant<V>;
+template <int V>
+using int_c = std::integral_constant<int, V>;
+// f(bool_c<b>{}): a run-time bool as a template argument (decltype(arg)::value inside a generic lambda)
+template <class F>
+static void with_bool(bool b, F&& f) {
+    if (b) f(bool_c<true>{});
+    else f(bool_c<false>{});
+}
+// f(int_c<V>{}) for the V of the list that equals v; the LAST one when none does (the list's default case)
+template <int V0, int... Vs, class F>
+static void with_int(int v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) f(int_c<V0>{});
+    else if (v == V0) f(int_c<V0>{});
+    else with_int<Vs...>(v, f);
+}
+
+#ifndef HK_OCC_SCALE_DEFAULT
+#define HK_OCC_SCALE_DEFAULT 1.0f
+#endif
+static inline int grid_for(int n, int block, int cap) {
+    long g = ((long)n + block - 1) / block;
+    if (g < 1) g = 1;
+    if (g > cap) g = cap;
+    return (int)g;
+}
+
+// blocks per CU that are actually resident for a kernel (occupancy API, capped): the wave-segment loop makes any
+// grid size correct, so the grid is sized to residency instead of oversubscribing and paying a tail round.
+template <class K>
+static int resident_blocks(K kernel, int block) {   // blocks per CU as the occupancy API reports them (uncapped)
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, 0) != hipSuccess || per_cu < 1) per_cu = 1;
+    return per_cu;
+}
+// HK_OCC_SCALE (round 6): the occupancy API of this ROCm answers HALF of what the register file admits for the 256-thread kernels here
+// (k_camera, 52 VGPRs: 4 blocks per CU where 512 / 56 registers give 8 waves per SIMD = 8 blocks; MI355X_MICROARCH.md "Register files").
+// Grids are sized by `answer x scale`, capped at the caller's cap (8 blocks = 32 waves per CU, the hardware's own limit) — a block the
+// CU cannot hold simply starts later, and the ticketed / strided segment loops make any grid size correct.
+static float occ_scale() {
+    const char* e = hk::knob("HK_OCC_SCALE");
+    const float v = e ? (float)std::atof(e) : HK_OCC_SCALE_DEFAULT;
+    return v >= 0.25f && v <= 8.0f ? v : 1.0f;
+}
+// Residency is a property of (kernel, device): cached per kernel instantiation AND per device, so one process can drive several
+// GPUs (the in-library multi-device path) without one device's answer leaking to another.
+#define HK_MAX_DEVICES 64
+template <auto Kernel>
+static int cached_blocks(int block, int n_cu, int cap_per_cu) {
+    static int cache[HK_MAX_DEVICES];
+    int dev = 0, per_cu;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= HK_MAX_DEVICES)
+        per_cu = resident_blocks(Kernel, block);
+    else {
+        if (cache[dev] == 0) {
+            cache[dev] = resident_blocks(Kernel, block);
+            if (hk::knob("HK_DEBUG_ALLOC")) std::fprintf(stderr, "HK_DEBUG_ALLOC occupancy API: %d blocks of %d per CU for %s\n", cache[dev], block, __PRETTY_FUNCTION__);
+        }
+        per_cu = cache[dev];
+    }
+    per_cu = (int)((float)per_cu * occ_scale() + 0.5f);
+    if (per_cu < 1) per_cu = 1;
+    if (per_cu > cap_per_cu) per_cu = cap_per_cu;
+    return per_cu * n_cu;
+}
+// Segments are walked with a static stride, so the number of physical waves must DIVIDE W or the last round runs with a
+// fraction of the waves (shade at W = 16/CU with 12 resident: 12 % slower than at W = 24): the largest divisor of the
+// 4-wave block count that is resident.
+static int clamp_blocks(int blocks, const DPathState& st, int waves_per_block = 4) {
+    const int units = st.n_waves / waves_per_block;
+    if (blocks >= units) return units;
+    if (st.dynamic_segments) return blocks;
+    int best = 1;
+    for (int b = blocks; b >= 1; --b)
+        if (units % b == 0) {
+            best = b;
+            break;
+        }
+    // a divisor far below residency wastes more than the tail round it avoids
+    return best * 4 >= blocks * 3 ? best : blocks;
+}
+// K(st, args...) over the wave segments of st: as many blocks as are resident (at most cap_per_cu per CU), clamped to the segment count.
+template <auto K, class... A>
+static void launch_resident(hipStream_t s, int n_cu, const DPathState& st, int block, int cap_per_cu, A&&... args) {
+    const int blocks = cached_blocks<K>(block, n_cu, cap_per_cu);
+    hipLaunchKernelGGL(K, dim3(clamp_blocks(blocks, st, block / 64)), dim3(block), 0, s, st, args...);
+}
+
+// ---- the A/B switches of the launch layer, looked up per launch in the context's knob table ----
+static bool node_cache_on() { return knob_on("HK_NODE_CACHE"); }           // 0: the lean kernels read every node from global memory
+static int grey_mode() { return knob_int("HK_GREY", 1); }                   // 0: flat-spectrum media run through the general tracking kernels
+static int grey_flat_mode() { return knob_int("HK_GREY_FLAT", 1); }         // 0: grey media run through the round-3 GREY instantiations of k_track / k_shadow_walk
+static int walk_pool_mode() { return knob_int("HK_WALK_POOL", 1); }         // 0: k_shadow_walk<.., GREY> instead of k_walk_pool; 1: 8-entry stacks where the tree allows; other: 16
+static int track_pool_mode() { return knob_int("HK_TRACK_POOL", 1); }       // 0: k_track_flat instead of k_track_pool
+// both sampler tables hold every draw of this bounce (rows up to 9 + 5 depth: sobol_row) for every path of the pass: the table-only
+// instantiations (HK_SOBOL_TABLE_ONLY=0: always the general ones)
+static bool sobol_tables_cover(const DSobol& sob, int depth) {
+    return sob.hi_table != nullptr && sob.lo_table != nullptr && 9 + 5 * depth < sob.lo_rows && 9 + 5 * depth < sob.hi_rows && knob_on("HK_SOBOL_TABLE_ONLY");
+}
+// media kernels are instantiated for a single medium kind or for all four (15)
+static int media_mask_class(const DScene& sc) {
+    int m = sc.media_mask;
+    return (m == 1 || m == 2 || m == 4 || m == 8) ? m : 15;
+}
+
+void launch_camera(hipStream_t s, int n_cu, const DPathState& st, const DFrame& fr, const DTables& T, const DFilter& flt, const DCamera& cam, const DSobol& sob, int initial_medium) {
+    launch_resident<k_camera>(s, n_cu, st, 256, 8, fr, T, flt, cam, sob, initial_medium);
+}
+
+// k_trace_lean over a BVH of depth <= 16: ONE 1024-thread block per CU (the 4 waves per SIMD its registers allow anyway) whose LDS
+// holds the 16 stacks (64 KB) and the top 1536 nodes of the tree (84 KB) — all of the Cornell box, the upper levels of the others.
+// Measured (HK_NODE_CACHE=0 switches it off): trace -11 % in the Cornell box and the sky scene; with the 32-entry stacks of the
+// 10^6-triangle scene 512 nodes are a small part of the visits (+-1 %: no cache there).
+// The any-hit kernel lives on residency (7 waves per SIMD on 16 KB of stacks; the big cache cost it three of them: +3 %), so it
+// gets the cache that FITS beside them.  Round 6 (two-spheres Cornell box, A B | B A): what counts is nodes per WAVE-SLOT — a cache is shared by the
+// waves of its block, so bigger blocks buy more of the tree for the same LDS.  12-wave blocks with the top 560 nodes (48 KB of stacks + 31 KB of
+// nodes, two blocks per CU = 6 waves per SIMD): k_shadow 17.55 -> 16.4 ms per Cornell frame, sky 2.6 -> 2.5.  On the way: 4-wave blocks with
+// 112 nodes (rounds 3-5, seven blocks per CU) 17.55, 176 nodes (six blocks) 17.0, 192 / 240 / 320 nodes (five, five, four blocks) 18.5 / 18.3 /
+// 20.3; 8-wave blocks with 384 nodes 20.2 and 14-wave blocks with 432 nodes 22.5 (one block short of the plan each); 16-wave blocks with the
+// whole tree (four waves per SIMD) 17.0.
+#ifndef HK_SHADOW_NC16
+#define HK_SHADOW_NC16 560
+#endif
+#ifndef HK_SHADOW_BLOCK16   // threads per block of the any-hit kernel over trees <= 16 deep
+#define HK_SHADOW_BLOCK16 768
+#endif
+#ifndef HK_SHADOW_NC32
+#define HK_SHADOW_NC32 0
+#endif
+#ifndef HK_TRACE_NC32
+#define HK_TRACE_NC32 128   // 10^6-triangle scene: trace -1.3 % (256 nodes cost a block per CU: +15 %)
+#endif
+// The instantiation of a lean kernel (k_trace_lean / k_shadow: <COUNT, STACK, BLOCK, NC, QN>) for this tree: launch(COUNT, STACK, BLOCK, NC, QN).
+// A tree at most 16 deep: 16-entry stacks, blocks of B16 threads that cache its top NC16 nodes; a deeper one: HK_LDS_STACK entries, NC32
+// nodes, and its quantised nodes (DScene::qnodes) where the scene has them.  HK_NODE_CACHE=0: no cache (honoured for the quantised tree too,
+// ADVICE r5), and then the plain block.
+template <int B16, int NC16, int NC32, class F>
+static void lean_dispatch(const DScene& sc, const DFrame& fr, F&& launch) {
+    with_bool(fr.count_nodes != 0, [&](auto COUNT) {
+        with_bool(node_cache_on(), [&](auto CACHE) {
+            constexpr bool cache = decltype(CACHE)::value;
+            if (sc.bvh_depth <= 16) launch(COUNT, int_c<16>{}, int_c<cache ? B16 : HK_TRACE_BLOCK>{}, int_c<cache ? NC16 : 0>{}, bool_c<false>{});
+            else with_bool(sc.qnodes != nullptr, [&](auto QN) { launch(COUNT, int_c<HK_LDS_STACK>{}, int_c<HK_TRACE_BLOCK>{}, int_c<cache ? NC32 : 0>{}, QN); });
+        });
+    });
+}
+void launch_trace(hipStream_t s, int n_cu, const DPathState& st, const DScene& sc, const DTables& T, const DFrame& fr, int depth, DStats* stats) {
+    if (lean_scene(sc)) {
+        lean_dispatch<1024, 1536, HK_TRACE_NC32>(sc, fr, [&](auto COUNT, auto STACK, auto BLOCK, auto NC, auto QN) {
+            constexpr int block = decltype(BLOCK)::value;
+            launch_resident<k_trace_lean<decltype(COUNT)::value, decltype(STACK)::value, block, decltype(NC)::value, decltype(QN)::value>>(s, n_cu, st, block, 8, sc, depth, stats);
+        });
+        return;
+    }
+    with_bool(fr.count_nodes != 0, [&](auto COUNT) { launch_resident<k_trace<decltype(COUNT)::value>>(s, n_cu, st, HK_TRACE_BLOCK, 8, sc, T, fr, depth, stats); });
+}
+template <bool C, int MM>
+static void launch_walk_split(hipStream_t s, int n_cu, const DPathState& st, const DScene& sc, const DFrame& fr, int depth, DStats* stats) {
+    const int cb = clamp_blocks(cached_blocks<k_walk_cast<C, MM, 16>>(HK_TRACE_BLOCK, n_cu, 8), st);
+    const int tb = clamp_blocks(cached_blocks<k_walk_track<MM>>(256, n_cu, 8), st);
+    for (int round = 0; round < HK_WALK_ROUNDS; ++round) {
+        hipLaunchKernelGGL((k_walk_cast<C, MM, 16>), dim3(cb), dim3(HK_TRACE_BLOCK), 0, s, st, sc, depth, round, stats, sc.media);
+        hipLaunchKernelGGL((k_walk_track<MM>), dim3(tb), dim3(256), 0, s, st, sc, depth, round, fr.walk_tune, stats, sc.media);
+    }
+}
+// The compact records (r_u == 1 not stored, r_l one float: DPathState::compact) also hold in a scene whose one medium is grey AND runs
+// through the pool kernels (k_track_pool / k_walk_pool, the only media kernels that know the compact layout): r_u is never touched
+// there and every factor of r_l is a scalar.  HK_GREY_COMPACT=0: the full records.
+bool grey_compact_ok(const DScene& sc) {
+    if (!knob_on("HK_GREY_COMPACT")) return false;
+    const int mc = sc.n_media > 0 ? media_mask_class(sc) : 0;
+    return sc.n_media == 1 && sc.all_grey && sc.grey_pool && (mc == 2 || mc == 8) && sc.bvh_depth <= 16 && grey_mode() && grey_flat_mode() && track_pool_mode() && walk_pool_mode() &&
+           !walk_split_mode();
+}
+// the shadow walk through surfaces that let rays pass and through media of class MM (0: no medium)
+template <bool C, int MM>
+static void launch_shadow_walk(hipStream_t s, int n_cu, const DPathState& st, const DScene& sc, const DTables& T, const DFrame& fr, int depth, DStats* stats) {
+    constexpr bool grey_kind = MM == 2 || MM == 8;   // the media kinds with GREY / pool instantiations
+    constexpr int M2 = grey_kind ? MM : 8;
+    const bool shallow = sc.bvh_depth <= 16;   // 16-entry stacks: 16 KB per block
+    const int pool = walk_pool_mode();
+    if (shallow && grey_kind && sc.grey_pool && grey_mode() && grey_flat_mode() && pool) {
+        if (M2 == 8 && sc.grey_bricks && sc.bvh_depth <= 8 && pool == 1)
+            launch_resident<k_walk_pool<C, 8, true, 8, 64>>(s, n_cu, st, HK_TRACE_BLOCK, 8, sc, depth, fr.walk_tune, fr.track_gate, stats, sc.media);
+        else if (M2 == 8 && sc.grey_bricks)
+            launch_resident<k_walk_pool<C, 8, true, 16, 56>>(s, n_cu, st, HK_TRACE_BLOCK, 8, sc, depth, fr.walk_tune, fr.track_gate, stats, sc.media);
+        else
+            launch_resident<k_walk_pool<C, M2, false, 16, 56>>(s, n_cu, st, HK_TRACE_BLOCK, 8, sc, depth, fr.walk_tune, fr.track_gate, stats, sc.media);
+    } else if (shallow && grey_kind && sc.all_grey && grey_mode())
+        launch_resident<k_shadow_walk<C, M2, 16, true>>(s, n_cu, st, HK_TRACE_BLOCK, 8, sc, T, depth, fr.walk_tune, stats, sc.media);
+    else if (shallow)
+        launch_resident<k_shadow_walk<C, MM, 16>>(s, n_cu, st, HK_TRACE_BLOCK, 8, sc, T, depth, fr.walk_tune, stats, sc.media);
+    else
+        launch_resident<k_shadow_walk<C, MM>>(s, n_cu, st, HK_TRACE_BLOCK, 8, sc, T, depth, fr.walk_tune, stats, sc.media);
+}
+void launch_shadow(hipStream_t s, int n_cu, const DPathState& st, const DScene& sc, const DTables& T, const DFrame& fr, int depth, DStats* stats) {
+    if (lean_scene(sc)) {
+        lean_dispatch<HK_SHADOW_BLOCK16, HK_SHADOW_NC16, HK_SHADOW_NC32>(sc, fr, [&](auto COUNT, auto STACK, auto BLOCK, auto NC, auto QN) {
+            constexpr int block = decltype(BLOCK)::value;
+            launch_resident<k_shadow<decltype(COUNT)::value, decltype(STACK)::value, block, decltype(NC)::value, decltype(QN)::value>>(s, n_cu, st, block, 8, sc, depth, stats);
+        });
+        return;
+    }
+    const int mc = sc.n_media > 0 ? media_mask_class(sc) : 0;
+    const bool split = sc.all_grey && grey_mode() && walk_split_mode() && sc.bvh_depth <= 16 && st.wq_a != nullptr;
+    with_bool(fr.count_nodes != 0, [&](auto COUNT) {
+        constexpr bool c = decltype(COUNT)::value;
+        if (split && mc == 8) launch_walk_split<c, 8>(s, n_cu, st, sc, fr, depth, stats);
+        else if (split && mc == 2) launch_walk_split<c, 2>(s, n_cu, st, sc, fr, depth, stats);
+        else with_int<0, 1, 2, 4, 8, 15>(mc, [&](auto MM) { launch_shadow_walk<c, decltype(MM)::value>(s, n_cu, st, sc, T, fr, depth, stats); });
+    });
+}
+// work lists of up to HK_MAX_KINDS + 6 queues (pairs depth, queue id) in one launch
+void launch_segment_lists(hipStream_t s, const DPathState& st, int n, const int* depths, const int* queues) {
+    if (n <= 0) return;
+    SegQueues qs;
+    qs.n = n;
+    for (int i = 0; i < n; ++i) {
+        qs.depth[i] = depths[i];
+        qs.q[i] = queues[i];
+    }
+    hipLaunchKernelGGL(k_segment_lists, dim3(n, HK_LIST_SPLIT), dim3(1024), 0, s, st, qs);
+}
+void launch_medium(hipStream_t s, int n_cu, const DPathState& st, const DScene& sc, const DTables& T, const DFrame& fr, const DSobol& sob, int depth, DStats* stats) {
+    {
+        const int d = depth, q = Q_MEDIUM;
+        launch_segment_lists(s, st, 1, &d, &q);
+    }
+    const bool grey = sc.all_grey && grey_mode();
+    const bool flat = grey && grey_flat_mode();
+    const bool pool = flat && track_pool_mode() && sc.grey_pool;
+    auto track = [&](auto MM, auto GREY) { launch_resident<k_track<decltype(MM)::value, decltype(GREY)::value>>(s, n_cu, st, 256, 8, sc, T, fr, depth, stats, sc.media); };
+    auto track_flat = [&](auto MM, auto BRICKS) {
+        constexpr int mm = decltype(MM)::value;
+        constexpr bool bricks = decltype(BRICKS)::value;
+        if (pool) launch_resident<k_track_pool<mm, bricks>>(s, n_cu, st, 256, 8, sc, fr, depth, stats, sc.media);
+        else launch_resident<k_track_flat<mm, bricks>>(s, n_cu, st, 256, 8, sc, fr, depth, stats, sc.media);
+    };
+    switch (media_mask_class(sc)) {   // (only homogeneous (2) and grid (8) media have grey instantiations, only grids have bricks)
+        case 1: track(int_c<1>{}, bool_c<false>{}); break;
+        case 2:
+            if (flat) track_flat(int_c<2>{}, bool_c<false>{});
+            else with_bool(grey, [&](auto GREY) { track(int_c<2>{}, GREY); });
+            break;
+        case 4: track(int_c<4>{}, bool_c<false>{}); break;
+        case 8:
+            if (flat) with_bool(sc.grey_bricks != 0, [&](auto BRICKS) { track_flat(int_c<8>{}, BRICKS); });
+            else with_bool(grey, [&](auto GREY) { track(int_c<8>{}, GREY); });
+            break;
+        default: track(int_c<15>{}, bool_c<false>{}); break;
+    }
+    {
+        const int d = depth, q = Q_SCATTER;
+        launch_segment_lists(s, st, 1, &d, &q);
+    }
+    with_bool(sobol_tables_cover(sob, depth), [&](auto FT) { launch_resident<k_scatter<decltype(FT)::value>>(s, n_cu, st, 256, 8, sc, T, fr, sob, depth, stats); });
+}
+void launch_detect_camera_medium(hipStream_t s, const DPathState& st, const DScene& sc, float x, float y, float z, DStats* stats) {
+    hipLaunchKernelGGL(k_detect_camera_medium, dim3(1), dim3(64), 0, s, st, sc, x, y, z, stats);
+}
+void launch_escaped(hipStream_t s, int n_cu, const DPathState& st, const DScene& sc, const DTables& T, const DFrame& fr, int depth) {
+    // HK_ESCAPED_UNROLL=2: two queue entries per lane and iteration (A/B switch; films bit-identical).  Measured, sky: 8.9 -> 10.4 ms per
+    // frame — its registers cost the kernel a block per CU (3 instead of 4); off.  (One wave per segment instead of the resident stride: +-0, sky)
+    with_bool(knob_int("HK_ESCAPED_UNROLL", 1) != 2, [&](auto ONE) { launch_resident<k_escaped<decltype(ONE)::value ? 1 : 2>>(s, n_cu, st, 256, 8, sc, T, depth, fr.implicit_ones); });
+}
+// scenes whose next-event light is chosen by k_light_select before the shade kernels run (HK_PRESELECT=0: never)
+bool preselect_lights(const DScene& sc, const DPathState& st) {
+    return sc.n_media == 0 && sc.num_bvh_lights >= HK_PRESELECT_MIN && st.sel_light != nullptr && knob_on("HK_PRESELECT");
+}
+void launch_light_select(hipStream_t s, int n_cu, const DPathState& st, const DScene& sc, const DTables& T, const DFrame& fr, const DSobol& sob, int depth, uint32_t kinds_mask, DStats* stats) {
+    const int min_idle = knob_int_in("HK_SELECT_MIN_IDLE", 1, 64, HK_SELECT_MIN_IDLE);
+    const bool pool = knob_on("HK_SELECT_POOL");   // 0: the per-lane-refill kernel of round 4 (A/B switch; films bit-identical)
+    with_bool(sobol_tables_cover(sob, depth), [&](auto FT) {
+        constexpr bool ft = decltype(FT)::value;
+        if (pool) launch_resident<k_light_select_pool<ft>>(s, n_cu, st, HK_SELECT_BLOCK, 8, sc, T, fr, sob, depth, kinds_mask, stats);
+        else launch_resident<k_light_select<ft>>(s, n_cu, st, 256, 8, sc, T, fr, sob, depth, kinds_mask, min_idle, stats);
+    });
+}
+void launch_shade(hipStream_t s, int n_cu, int kind, const DPathState& st, const DScene& sc, const DTables& T, const DFrame& fr, const DSobol& sob, int depth, int first_kind, DStats* stats) {
+    auto shade = [&](auto KIND, auto SIMPLE, auto FT, auto PRE) {
+        launch_resident<k_shade<decltype(KIND)::value, decltype(SIMPLE)::value, decltype(FT)::value, decltype(PRE)::value>>(s, n_cu, st, 256, 8, sc, T, fr, sob, depth, first_kind, stats);
+    };
+    const bool ft = sobol_tables_cover(sob, depth);
+    // the kinds with next-event instantiations of their own (table-only draws, a light chosen beforehand); the others run k_shade<KIND>
+    const bool light_kind = kind == HK_MAT_MATTE || kind == HK_MAT_MIRROR || kind == HK_MAT_GLASS || kind == HK_MAT_CONDUCTOR;
+    if (light_kind && preselect_lights(sc, st))   // k_light_select has run for this depth: the instantiations without the light-BVH descent
+        with_int<HK_MAT_MATTE, HK_MAT_MIRROR, HK_MAT_GLASS, HK_MAT_CONDUCTOR>(kind, [&](auto KIND) { with_bool(ft, [&](auto FT) { shade(KIND, bool_c<false>{}, FT, bool_c<true>{}); }); });
+    else if (kind == HK_MAT_MATTE && sc.simple_lights)
+        with_bool(ft, [&](auto FT) { shade(int_c<HK_MAT_MATTE>{}, bool_c<true>{}, FT, bool_c<false>{}); });
+    else if (light_kind && ft)
+        with_int<HK_MAT_MATTE, HK_MAT_MIRROR, HK_MAT_GLASS, HK_MAT_CONDUCTOR>(kind, [&](auto KIND) { shade(KIND, bool_c<false>{}, bool_c<true>{}, bool_c<false>{}); });
+    else
+        with_int<HK_MAT_MATTE, HK_MAT_MIRROR, HK_MAT_GLASS, HK_MAT_CONDUCTOR, HK_MAT_COATED_DIFFUSE, HK_MAT_THIN_DIELECTRIC, HK_MAT_DIFFUSE_TRANSMISSION, HK_MAT_COATED_DIFFUSE_TRANSMISSION,
+                 HK_MAT_COATED_CONDUCTOR, HK_MAT_FALLBACK>(kind, [&](auto KIND) { shade(KIND, bool_c<false>{}, bool_c<false>{}, bool_c<false>{}); });
+}
+// k_small_pass: the whole pass of a small call in one launch.
+#ifndef HK_SMALL_PASS_NC
+#define HK_SMALL_PASS_NC 1536
+#endif
+// the scenes k_small_pass is instantiated for (the pass itself must be a small one: launch_small_pass): -> 0 none, 1 the all-matte closed
+// scene under simple lights, 2 the general instantiation (Matte / Mirror / Glass / Conductor, escape lights)
+static int small_pass_class(const DScene& sc, uint32_t kinds_mask) {
+    const int mode = knob_int("HK_SMALL_PASS_FUSED", 2);   // 0: the stages as launches, 1: only the all-matte instantiation (A/B switch; films bit-identical)
+    if (mode == 0) return 0;
+    if (!(lean_scene(sc) && sc.bvh_depth <= HK_LDS_STACK && node_cache_on())) return 0;
+    if (kinds_mask == (1u << HK_MAT_MATTE) && sc.simple_lights && !sc.has_escape_lights && sc.bvh_depth <= 16 && sc.num_bvh_lights < HK_PRESELECT_MIN) return 1;
+    const uint32_t light_kinds = (1u << HK_MAT_MATTE) | (1u << HK_MAT_MIRROR) | (1u << HK_MAT_GLASS) | (1u << HK_MAT_CONDUCTOR);
+    return (mode >= 2 && kinds_mask != 0 && (kinds_mask & ~light_kinds) == 0) ? 2 : 0;
+}
+bool small_pass_fusable(const DScene& sc, uint32_t kinds_mask) { return small_pass_class(sc, kinds_mask) != 0; }
+// one block per CU (its LDS: 16-entry stacks, the top of the tree, the emission lists) of as many waves as the pass has segments per CU;
+// -> false when the pass has fewer segments than one block's waves
+template <int BLOCK, bool GENERAL, int STACK, class... A>
+static bool small_pass_blocks(hipStream_t s, int n_cu, const DPathState& st, bool dry, A&&... args) {
+    constexpr auto kernel = k_small_pass<HK_SMALL_PASS_NC, BLOCK, GENERAL, STACK>;
+    int blocks = cached_blocks<kernel>(BLOCK, n_cu, 1);
+    if (blocks * (BLOCK / 64) > st.n_waves) blocks = st.n_waves / (BLOCK / 64);
+    if (blocks < 1) return false;
+    if (!dry) hipLaunchKernelGGL(kernel, dim3(blocks), dim3(BLOCK), 0, s, st, args...);
+    return true;
+}
+bool launch_small_pass(hipStream_t s, int n_cu, const DPathState& st, const DScene& sc, const DTables& T, const DFrame& fr, const DFilter& flt, const DCamera& cam, const DSobol& sob, int max_depth,
+                       uint32_t kinds_mask, DStats* stats, bool dry, void* accum, int film_mode) {
+    const int cls = small_pass_class(sc, kinds_mask);
+    if (cls == 0 || !st.small_pass || st.dynamic_segments || fr.count_nodes) return false;
+    // a SMALL pass in ensure_state's sense (at most 16 chunks for each of 4 waves per CU), not the mid-size pass that shares its static
+    // segments: with 25 chunks per stage the launches' higher residency wins (800^2 x 32 spp without sampler tables: 14.8 ms as launches, 17.2 here)
+    if (((long)st.capacity + 63) / 64 / 16 > 4L * n_cu) return false;
+    for (int depth = 0; depth < max_depth; ++depth)
+        if (sobol_tables_cover(sob, depth)) return false;
+    const int merged = knob_on("HK_SMALL_PASS_MERGED") ? 1 : 0;   // 0: shadow rays and the next bounce's rays as two stages (A/B switch; films bit-identical)
+    // (Cornell 800^2, one sample per call: 1.42 / 1.05 / 1.14 ms at 4 / 8 / 16 segments per CU — 256- / 512- / 1024-thread blocks; a 768-thread
+    // block for 12: 1.55.  Eight waves per CU hold 312 paths each: chunks stay fuller down the bounces than with 156, and at two waves per
+    // SIMD nothing spills.)
+    // two waves per SIMD at most: at 16 segments per CU (1 024-thread blocks, 128 registers) the matte instantiation spilled 372 B per lane
+    // and lost to 8 (1.14 ms against 1.05), the general one does not fit at all — such a pass keeps the launches
+    if (st.n_waves > 8 * n_cu) return false;
+    bool launched = false;
+    auto pass = [&](auto GENERAL, auto STACK) {   // 512-thread blocks for 8 segments per CU, 256-thread blocks for 4
+        with_bool(st.n_waves > 4 * n_cu, [&](auto WIDE) {
+            launched = small_pass_blocks<decltype(WIDE)::value ? 512 : 256, decltype(GENERAL)::value, decltype(STACK)::value>(s, n_cu, st, dry, sc, T, fr, flt, cam, sob, max_depth, sc.n_lights > 0 ? 1 : 0, merged,
+                                                                                                                       accum, film_mode, kinds_mask, stats);
+        });
+    };
+    if (cls == 2 && sc.bvh_depth > 16) pass(bool_c<true>{}, int_c<HK_LDS_STACK>{});
+    else if (cls == 2) pass(bool_c<true>{}, int_c<16>{});
+    else pass(bool_c<false>{}, int_c<16>{});
+    return launched;
+}
+void launch_film(hipStream_t s, const DPathState& st, const DFrame& fr, const DTables& T, void* accum, bool f64) {
+    int g = grid_for(fr.n_pixels_padded >> 6, 4, 4096);   // one wave per 8x8 tile
+    if (f64)
+        hipLaunchKernelGGL(k_film<double>, dim3(g), dim3(256), 0, s, st, fr, T, (double*)accum);
+    else
+        hipLaunchKernelGGL(k_film<float>, dim3(g), dim3(256), 0, s, st, fr, T, (float*)accum);
+}
+void launch_finalize(hipStream_t s, const void* accum, bool f64, float* out, int w, int h) {
+    int g = grid_for(w * h, 256, 4096);
+    if (f64)
+        hipLaunchKernelGGL(k_finalize<double>, dim3(g), dim3(256), 0, s, (const double*)accum, out, w, h);
+    else
+        hipLaunchKernelGGL(k_finalize<float>, dim3(g), dim3(256), 0, s, (const float*)accum, out, w, h);
+}
+void launch_sobol_table(hipStream_t s, const DSobol& sob, const DFrame& fr, uint2* table, int rows) {
+    hipLaunchKernelGGL(k_sobol_table, dim3(grid_for((long)rows * fr.n_pixels_padded > 0x3fffffff ? 0x3fffffff : rows * fr.n_pixels_padded, 256, 8192)), dim3(256), 0, s, sob, fr, table, rows);
+}
+void launch_sobol_lo_table(hipStream_t s, const DSobol& sob, const DFrame& fr, uint16_t* table, int rows, int base, int stride, int count) {
+    hipLaunchKernelGGL(k_sobol_lo_table, dim3(65536), dim3(256), 0, s, sob, fr, table, rows, base, stride, count);
+}
+void launch_postprocess(hipStream_t s, const hk_postprocess_params& P, const float* src, const float* depth, float* dst, int h, int w) {
+    hipLaunchKernelGGL(k_postprocess, dim3(grid_for(h * w, 256, 8192)), dim3(256), 0, s, P, src, depth, dst, h, w);
+}
+void launch_denoise_variance(hipStream_t s, const float* src, float* variance, int h, int w) {
+    hipLaunchKernelGGL(k_denoise_variance, dim3(grid_for(h * w, 256, 8192)), dim3(256), 0, s, src, variance, h, w);
+}
+void launch_denoise_atrous(hipStream_t s, const hk_denoise_params& P, int step, const float* src, const float* normal, const float* depth, const float* variance,
+                           float* dst, int h, int w) {
+    hipLaunchKernelGGL(k_denoise_atrous, dim3(grid_for(h * w, 256, 8192)), dim3(256), 0, s, P, step, src, normal, depth, variance, dst, h, w);
+}
+void launch_slot_of_prim(hipStream_t s, const float4* leaf, int n, int* slot_of_prim) {
+    hipLaunchKernelGGL(k_slot_of_prim, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, leaf, n, slot_of_prim);
+}
+void launch_xform_tris(hipStream_t s, const DXform& X, int first, int n, const float* bp, const float* bn, const float* bt, const int* slot_of_prim, float* pos, float* nrm,
+                       float* tan, float* shade, float4* leaf) {
+    hipLaunchKernelGGL(k_xform_tris, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, X, first, n, bp, bn, bt, slot_of_prim, pos, nrm, tan, shade, leaf);
+}
+void launch_refit_level(hipStream_t s, int begin, int end, DNode* nodes, DQNode* qnodes, const DQGrid& grid, const float4* leaf, const float* pos) {
+    hipLaunchKernelGGL(k_refit_level, dim3(grid_for(end - begin, 256, 8192)), dim3(256), 0, s, begin, end, nodes, qnodes, grid, leaf, pos);
+}
+void launch_aux(hipStream_t s, const DScene& sc, const DCamera& cam, int h, int w, float miss_depth, float* albedo, float* normal, float* depth) {
+    hipLaunchKernelGGL(k_aux, dim3(grid_for(h * w, HK_TRACE_BLOCK, 2048)), dim3(HK_TRACE_BLOCK), 0, s, sc, cam, h, w, miss_depth, albedo, normal, depth);
+}
+
+}  // namespace hk

@@ -10,11 +10,25 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cstdlib>
 
 // Run-time knobs (hk_api.cpp): the value of HK_<name> in the table of the context whose entry point runs on this thread, or nullptr.
 // The environment is read once, by hk_ctx_create; hk_ctx_set_option changes a knob afterwards.
+// The three ways a knob is read (a value that is not a number reads as 0, as atoi has it):
 namespace hk {
 const char* knob(const char* name);
+inline bool knob_on(const char* name) {   // a switch that is on unless set to 0
+    const char* e = knob(name);
+    return !(e && std::atoi(e) == 0);
+}
+inline int knob_int(const char* name, int dflt) {   // the integer as written; dflt when unset
+    const char* e = knob(name);
+    return e ? std::atoi(e) : dflt;
+}
+inline int knob_int_in(const char* name, int lo, int hi, int dflt) {   // dflt when unset or outside [lo, hi]
+    const int v = knob_int(name, dflt);
+    return v >= lo && v <= hi ? v : dflt;
+}
 }
 
 #define HK_TICKET_COLS 16       // kernels per bounce that draw segment tickets (5 + HK_MAX_KINDS)

@@ -246,3 +246,28 @@ def test_bvh_builder_invariants(n_tris):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", os.path.join(root, "include"), "-I", os.path.join(root, "hikari.jl_amd", "csrc")] + src + ["-o", exe])
     r = subprocess.run([exe, str(n_tris), "11"], capture_output=True, text=True)
     assert r.returncode == 0 and r.stdout.startswith("ok"), (r.stdout, r.stderr)
+
+
+def test_knob_names_read_equal_knob_names_listed():
+    """KNOB_NAMES (hk_api.cpp) is the list of record: hk_ctx_create copies exactly these from the environment and the option calls refuse
+    every other name.  Every "HK_..." name the sources hand to hk::knob or to a typed reader (knob_on / knob_int / knob_int_in, hk_types.h)
+    must be on it — a name that is read but not listed can never be set — and every listed name must be read somewhere."""
+    csrc = os.path.join(ROOT, "hikari.jl_amd", "csrc")
+    api = open(os.path.join(csrc, "hk_api.cpp")).read()
+    listed = re.search(r"KNOB_NAMES\[\]\s*=\s*\{(.*?)\};", api, re.S)
+    assert listed, "KNOB_NAMES not found"
+    names = re.findall(r'"(HK_[A-Z0-9_]+)"', listed.group(1))
+    assert len(names) == len(set(names)), "a knob is listed twice"
+    read = set()
+    for fn in sorted(os.listdir(csrc)):
+        if fn.endswith((".cpp", ".hip", ".h")):
+            read |= set(re.findall(r'\bknob(?:_on|_int|_int_in)?\(\s*"(HK_[A-Z0-9_]+)"', re.sub(r"//.*", "", open(os.path.join(csrc, fn)).read())))   # (comments cite knob("HK_X"))
+    print("read, not listed:", sorted(read - set(names)), " listed, not read:", sorted(set(names) - read))
+    assert read == set(names)
+    # a name that is not listed is refused by both option calls, before anything is stored or looked up
+    assert "HK_NO_SUCH_KNOB" not in names
+    for entry in ("hk_ctx_set_option", "hk_ctx_get_option"):
+        body = api[api.index('extern "C" int32_t %s(' % entry):]
+        body = body[:body.index("\n}\n")]
+        refuse = body.find('if (!hk::known_knob(name)) return fail(HK_ERR_INVALID, std::string("unknown option ") + name);')
+        assert refuse >= 0 and "knobs.kv" not in body[:refuse], entry
