@@ -1065,7 +1065,7 @@ HKD Surface surface_at(const DScene& sc, int prim, float bu, float bv, v3 ro, v3
     float w = 1.0f - bu - bv;
     s.pi = ro + rd * t;
     // (only the shading and light-selection kernels read the packed record: in the traversal kernels the second address path cost
-    // k_trace_lean 1.6 ms per Cornell frame without ever being taken, and scenes whose attributes fit in L2 gain nothing — hk_api.cpp
+    // k_trace_lean 1.6 ms per Cornell frame without ever being taken, and scenes whose attributes fit in L2 gain nothing — hk_scene.cpp
     // builds the records for scenes of >= 32 768 triangles)
     v3 a, b, c;
     if (sc.tri_shade) {

@@ -1,0 +1,355 @@
+// hk_host.h — what the host-side translation units share (hk_ctx / hk_scene / hk_scene_edit / hk_film / hk_render / hk_test_api /
+// hk_comm .cpp): the error slot, the knob scope, device buffers and the slab cache, the four opaque handle structs of the C-ABI and the
+// few helpers more than one file calls.  Private to csrc/ and not installed.  Everything declared here has hidden visibility: the
+// library exports the hk_* entry points of include/hikari_mi355x.h and nothing of this.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <limits>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "bvh_build.h"
+#include "hikari_mi355x.h"
+#include "hk_launch.h"
+#include "hk_nanovdb.h"
+#include "hk_types.h"
+
+#pragma GCC visibility push(hidden)
+
+// the message of the last failing call on this thread, whichever file that call is in (hk_last_error); defined in hk_ctx.cpp
+extern thread_local std::string g_err;
+inline int fail(int code, const std::string& msg) {
+    g_err = msg;
+    return code;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// RUN-TIME KNOBS.  The library never calls getenv on a render path: hk_ctx_create copies the HK_* variables it knows from the
+// environment ONCE into the context, hk_ctx_set_option changes one afterwards, and the code asks hk::knob("HK_X") — a lookup in the
+// table of the context whose entry point is running on this thread (KnobScope).  A host that setenv()s beside a render is harmless.
+// ---------------------------------------------------------------------------------------------------
+namespace hk {
+struct Knobs {
+    std::unordered_map<std::string, std::string> kv;
+};
+}  // namespace hk
+struct KnobScope {   // the knobs of `k` answer hk::knob on this thread until the scope ends (entry points nest: the outer one is restored)
+    const hk::Knobs* prev;
+    explicit KnobScope(const hk::Knobs* k);
+    ~KnobScope();
+};
+#define HIP_TRY(expr)                                                                                          \
+    do {                                                                                                       \
+        hipError_t e_ = (expr);                                                                                \
+        if (e_ != hipSuccess) return fail(HK_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+// PATH-STATE SLABS outlive the integrator that asked for them: the ~40 arrays of a path state are carved from one allocation, and a slab
+// that is let go is kept (per device, up to HK_STATE_CACHE_GB = 128 in total, the smallest ones dropped first) for the next path state
+// that fits it.  Two reasons, both measured on the cloud config (DESIGN.md §5 "two speeds"): allocating 84 GB takes 0.7 - 4 s, and where
+// the driver places a LATER big allocation decides whether the gather-heavy kernels run 7 - 9 % slower for the life of that integrator.
+// Everything cached is given back when a hipMalloc fails (then retried) and when a context of that device is destroyed.
+struct SlabCache {
+    struct Entry {
+        void* p;
+        size_t bytes;
+        int dev;
+    };
+    std::mutex m;
+    std::vector<Entry> free_list;
+    size_t cap_bytes = (size_t)128 << 30;   // HK_STATE_CACHE_GB (process-wide: the last context created / option set decides)
+    size_t cap() const { return cap_bytes; }
+    size_t total(int dev) {
+        std::lock_guard<std::mutex> g(m);
+        size_t t = 0;
+        for (const Entry& e : free_list) t += e.dev == dev ? e.bytes : 0;
+        return t;
+    }
+    void* take(int dev, size_t need, size_t& got) {   // the smallest slab that holds `need` without being more than twice as large
+        std::lock_guard<std::mutex> g(m);
+        int best = -1;
+        for (int i = 0; i < (int)free_list.size(); ++i) {
+            const Entry& e = free_list[i];
+            if (e.dev == dev && e.bytes >= need && e.bytes <= 2 * need + ((size_t)64 << 20) && (best < 0 || e.bytes < free_list[best].bytes)) best = i;
+        }
+        if (best < 0) return nullptr;
+        void* p = free_list[best].p;
+        got = free_list[best].bytes;
+        free_list.erase(free_list.begin() + best);
+        return p;
+    }
+    void give(int dev, void* p, size_t bytes) {
+        std::vector<void*> drop;
+        {
+            std::lock_guard<std::mutex> g(m);
+            free_list.push_back(Entry{p, bytes, dev});
+            size_t t = 0;
+            for (const Entry& e : free_list) t += e.bytes;
+            const size_t limit = cap();
+            while (!free_list.empty() && (t > limit || free_list.size() > 8)) {   // the smallest goes first: the big ones are the expensive ones
+                int k = 0;
+                for (int i = 1; i < (int)free_list.size(); ++i)
+                    if (free_list[i].bytes < free_list[k].bytes) k = i;
+                t -= free_list[k].bytes;
+                drop.push_back(free_list[k].p);
+                free_list.erase(free_list.begin() + k);
+            }
+        }
+        for (void* q : drop) (void)hipFree(q);
+    }
+    void trim(int dev) {   // dev < 0: every device
+        std::vector<void*> drop;
+        {
+            std::lock_guard<std::mutex> g(m);
+            for (int i = (int)free_list.size() - 1; i >= 0; --i)
+                if (dev < 0 || free_list[i].dev == dev) {
+                    drop.push_back(free_list[i].p);
+                    free_list.erase(free_list.begin() + i);
+                }
+        }
+        for (void* q : drop) (void)hipFree(q);
+    }
+};
+extern SlabCache g_slabs;
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    int slab_dev = -1;   // >= 0: a path-state slab of that device (goes back to g_slabs, not to the driver)
+    void release() {
+        if (p && slab_dev >= 0) {
+            // hipFree would have waited for the kernels that still use the memory; a slab goes back to the cache instead, so its OWNER
+            // waits first — for the streams of its own context only (quiesce), not for every stream of the host application
+            g_slabs.give(slab_dev, p, bytes);
+        } else if (p)
+            (void)hipFree(p);
+        p = nullptr, bytes = 0, slab_dev = -1;
+    }
+    ~DevBuf() { release(); }
+    hipError_t alloc(size_t n) {
+        release();
+        bytes = n;
+        if (n == 0) return hipSuccess;
+        hipError_t e = hipMalloc(&p, n);
+        if (e != hipSuccess) {   // the cached slabs are memory too
+            (void)hipGetLastError();
+            g_slabs.trim(-1);
+            e = hipMalloc(&p, n);
+        }
+        if (e != hipSuccess) p = nullptr, bytes = 0;
+        return e;
+    }
+    hipError_t alloc_slab(int dev, size_t n) {   // a cached slab that fits, or a new one
+        release();
+        size_t got = 0;
+        if (void* q = g_slabs.take(dev, n, got)) {
+            p = q, bytes = got, slab_dev = dev;
+            return hipSuccess;
+        }
+        const hipError_t e = alloc(n);
+        if (e == hipSuccess) slab_dev = dev;
+        return e;
+    }
+    hipError_t upload(const void* src, size_t n) {
+        hipError_t e = alloc(n ? n : 4);
+        if (e != hipSuccess) return e;
+        if (n) e = hipMemcpy(p, src, n, hipMemcpyHostToDevice);
+        return e;
+    }
+    template <class T>
+    T* as() const {
+        return reinterpret_cast<T*>(p);
+    }
+};
+
+struct hk_ctx {
+    int device = 0;
+    hk::Knobs knobs;                      // HK_* as of hk_ctx_create, then hk_ctx_set_option
+    bool own_stream_order = true;         // false: the caller handed hk_ctx_create a stream of its own and may order work after a render with stream / event calls
+    hipStream_t stream = nullptr;
+    hipStream_t aux = nullptr;            // second stream: the shadow rays of bounce d run beside the traversal of bounce d + 1
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    int overlap = -1;                     // the shadow kernels on a second stream: -1 auto (scenes with a deep BVH), HK_OVERLAP=0 / 1 never / always
+    int small_streak = 0;                 // consecutive small one-pass render calls so far (the lanes start after HK_PIPELINE_AFTER of them)
+    int n_cu = 256;
+    int waves_per_cu = 0;      // HK_WAVES_PER_CU: fixed number of wave segments per CU (0 = sized from the pass)
+    int stat_rows = 8192;      // DStats rows, indexed by PHYSICAL wave: n_cu * 32 (8 waves x 4 SIMDs is the residency limit)
+    DevBuf sobol, cie, r2s_scale, r2s_coeffs, r2s_points, stats;
+    DTables tables{};
+    bool have_tables = false;
+    std::vector<float> h_r2s_scale, h_r2s_coeffs;
+    hk::RGB2Spec r2s_host;
+    int count_nodes = 0, time_kernels = 0;
+    unsigned long long fused_passes = 0;   // passes rendered by k_small_pass (one launch)
+    // timing
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> trace_events;   // class 0
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> class_events[6];  // 1 shadow, 2 shade, 3 other, 4 media, 5 light selection (reported inside the shade class AND on its own)
+    uint64_t shadow_launches = 0, shade_launches = 0, media_launches = 0, select_launches = 0;
+    std::vector<hipEvent_t> event_pool;
+    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
+    bool have_span = false;
+    double seconds_trace = 0.0, seconds_total = 0.0;
+    uint64_t trace_launches = 0;
+    DStats host_stats{};
+    // PIPELINED SMALL PASSES.  A one-sample call (the reference's render!, volpath.jl:445-450: what an interactive viewer drives) puts
+    // < 1 path per resident lane in flight: its ~45 launches are each bound by the latency of ONE wave's chunk (50 - 90 us at any
+    // path count, profiles/r04_progressive_timeline.txt), the chip idles.  Such calls are independent of each other (another sample
+    // index of the same scene), so consecutive small calls go to HK_PIPELINE (default 4) LANES in turn — a stream, a path-state set
+    // and a statistics block each — and run beside each other; only the film kernels are chained (sums in call order: the film stays
+    // bit-identical to the sequential one).  Whatever reads or rewrites film / state / scene on the context's stream joins the
+    // lanes first (join_lanes).
+    struct Lane {
+        hipStream_t stream = nullptr;
+        hipEvent_t done = nullptr;
+        DevBuf stats;
+    };
+    enum { MAX_LANES = 16 };
+    Lane lanes[MAX_LANES];        // (created on first use)
+    int next_lane = 0;
+    // SMALL RENDER CALLS ARE BATCHED (hk_render_tile): consecutive one-pass calls that continue each other — same scene, integrator, film,
+    // camera, pixel range and stride, sample indices following on — are only noted here and rendered as ONE pass when something looks
+    // (flush_pending: every entry point that reads or rewrites film / statistics / scene / integrator, hk_sync, a call that does not fit)
+    struct Pending {
+        bool active = false;
+        hk_scene* sc = nullptr;
+        hk_integrator* I = nullptr;
+        hk_film* film = nullptr;
+        hk_camera cam{};
+        int first = 0, n = 0, stride = 1, x0 = 0, y0 = 0, x1 = 0, y1 = 0, calls = 0;
+    } pending;
+    bool lanes_dirty = false;     // a lane holds work the context's stream has not waited for
+    bool film_chain = false;      // ev_film marks the last film kernel of a lane
+    hipEvent_t ev_main = nullptr, ev_film = nullptr;
+};
+
+// every stream this context has launched on is idle afterwards (before path-state memory changes hands); other streams of the process are not touched
+void quiesce(hk_ctx* c);
+// the noted small calls are rendered (hk_render.cpp)
+int flush_pending(hk_ctx* c);
+// the context's stream waits for everything the lanes were given (cheap when nothing is pending)
+int join_lanes(hk_ctx* c);
+hipEvent_t get_event(hk_ctx* c);   // from the context's pool
+DCamera make_camera(const hk_camera& c);
+
+struct hk_scene {
+    hk_ctx* ctx = nullptr;
+    DevBuf nodes, qnodes, leaf_tris, positions, normals, uvs, tangents, meta, tri_shade, materials, textures, spectra, mis, lights, lnodes, trails, infinite;
+    DevBuf envmaps;
+    DevBuf media;
+    DScene d{};
+    uint32_t kinds_mask = 0;
+    int n_materials = 0;
+    int bvh_nodes = 0, bvh_leaf_tris = 0, bvh_depth = 0;
+    hk::LightBVH lbvh;
+    // ---- in-place edits (hk_scene_set_transform, hk_scene_update_materials) ----
+    std::vector<hk_material> h_materials;   // the records as created / last updated: what an update is checked against
+    int n_textures = 0, n_spectra = 0;
+    std::vector<int> level_start;           // breadth-first node levels: level L is [level_start[L], level_start[L + 1])
+    DevBuf base_pos, base_nrm, base_tan, slot_of_prim;   // geometry as created and the leaf slot of every triangle (first transform)
+    bool have_base = false;
+    bool qnodes_built = false;              // s->qnodes holds a quantised tree (D.qnodes is null while no grid is known to contain it)
+    enum { XF_BLOCK = 1024 };
+    std::vector<float> block_box;           // deep trees: lo[3] hi[3] of the base positions of every XF_BLOCK triangles
+    struct Xf {
+        int end;
+        bool identity;
+        float m[12];
+    };
+    std::map<int, Xf> xf;                   // transform of every triangle interval [key, end): the grid of the quantised nodes
+    struct Staging {                        // pinned upload buffers of material records, reused once their copy has run
+        void* host = nullptr;
+        size_t bytes = 0;
+        hipEvent_t ev = nullptr;
+    };
+    std::vector<Staging> staging;
+    // the arrays the records above point into (texels, spectra, envmap tables, medium grids): freed with the scene, after the staging
+    // events below have been waited for (the destructor's body runs before the members go)
+    std::vector<std::unique_ptr<DevBuf>> owned;
+    DevBuf& own() {
+        owned.emplace_back(new DevBuf());
+        return *owned.back();
+    }
+    ~hk_scene() {
+        for (auto& st : staging) {
+            if (st.ev) (void)hipEventSynchronize(st.ev), (void)hipEventDestroy(st.ev);
+            if (st.host) (void)hipHostFree(st.host);
+        }
+    }
+};
+// hk_scene.cpp; hk_scene_update_materials bakes and classifies with the same two
+void bake_material(const hk::RGB2Spec& t, const hk_material& m, DMaterial& o);
+bool material_alpha_tested(const hk_material& m);
+
+struct hk_film {
+    hk_ctx* ctx = nullptr;
+    int width = 0, height = 0;
+    bool f64 = false;
+    DevBuf own;
+    void* accum = nullptr;  // device
+    bool external = false;  // the caller owns `accum` (and may read it behind stream / event ordering of its own)
+    bool exposed = false;   // hk_film_accum_device_ptr handed the accumulators out: the caller may keep the pointer, so calls into this film are never only noted
+    DevBuf readback;
+    // hk_film_read_rgb / _async: the finalized frame lands in PINNED host memory (two buffers in turn), or straight in the caller's
+    // buffer when the caller named it with hk_film_pin_host (HK_READBACK_PIN=1: also a pointer that has come twice in a row)
+    float* staging[2] = {nullptr, nullptr};
+    int staging_next = 0, staging_last = -1;   // which buffer the next async read fills / the last one filled
+    bool read_in_flight = false;
+    hipEvent_t ev_read = nullptr;
+    void* last_out = nullptr;       // the caller's buffer of the previous synchronous read
+    void* pinned_user = nullptr;    // ... registered with the driver (hipHostRegister) — the copy goes there directly
+    bool pinned_explicit = false;   // registered by hk_film_pin_host (stays until hk_film_unpin_host / hk_film_destroy)
+    void* pin_failed = nullptr;     // HK_READBACK_PIN=1: the pointer whose registration the driver refused (not retried every frame)
+};
+
+struct hk_integrator {
+    hk_ctx* ctx = nullptr;
+    hk_integrator_params p{};
+    DFilter filter{};
+    DevBuf f_func, f_mcdf, f_mfunc, f_ccdf;
+    // path state (the reference's VolPathState, volpath-state.jl:29-181)
+    DPathState st{};
+    std::vector<std::unique_ptr<DevBuf>> bufs;
+    int st_capacity = 0, st_depth = 0, st_media = -1;   // what the retained path state was allocated for
+    bool mid_pass = false;                              // the current pass is a mid-size one of a closed scene (ensure_state): static stride, one stream
+    int slab_mode = 0;         // 0: one allocation per array; 1: measuring the slab; 2: carving it
+    void* slab_base = nullptr;
+    size_t slab_off = 0;
+    DevBuf sobol_table;  // DSobol::hi_table
+    int sobol_rows = 0, sobol_stride = 0, sobol_log2 = -1, sobol_digits = -1, sobol_x0 = -1, sobol_y0 = -1, sobol_tiles_x = -1;
+    DevBuf sobol_lo;     // DSobol::lo_table
+    int lo_rows = 0, lo_base = -1, lo_sample_stride = -1, lo_count = 0;
+    // the path-state sets of the context's lanes (pipelined small passes); a render on lane l swaps set l in for the duration of the call
+    struct StateSet {
+        DPathState st{};
+        std::vector<std::unique_ptr<DevBuf>> bufs;
+        int st_capacity = 0, st_depth = 0, st_media = -1;
+    };
+    std::vector<StateSet> lane_sets;
+    void swap_set(StateSet& o) {
+        std::swap(st, o.st);
+        std::swap(bufs, o.bufs);
+        std::swap(st_capacity, o.st_capacity);
+        std::swap(st_depth, o.st_depth);
+        std::swap(st_media, o.st_media);
+    }
+};
+// hk_render.cpp (the sampler parameters of a film; hk_test_sobol / hk_test_camera build the same)
+int ceil_log2(long v);
+DSobol make_sobol(const hk_integrator_params& p, int w, int h);
+
+struct hk_comm {
+    std::vector<hk_ctx*> ctxs;     // local ranks of this process (1 in the one-process-per-GPU layout)
+    std::vector<void*> comms;      // ncclComm_t per local rank
+    int world = 1;
+};
+
+#pragma GCC visibility pop

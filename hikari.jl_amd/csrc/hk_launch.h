@@ -1,5 +1,5 @@
 // hk_launch.h — the launch layer: which kernel instantiation runs for a scene, a pass and a knob table.  Defined in hk_launch_impl.h and
-// hk_test_kernels.h (both part of the hk_kernels.hip translation unit), called from hk_api.cpp.  This is the only declaration of it.
+// hk_test_kernels.h (both part of the hk_kernels.hip translation unit), called from the host files (hk_render.cpp, hk_film.cpp, hk_scene_edit.cpp, hk_test_api.cpp).  This is the only declaration of it.
 #pragma once
 #include "hikari_mi355x.h"
 #include "hk_types.h"

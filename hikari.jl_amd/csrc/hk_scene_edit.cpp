@@ -1,0 +1,205 @@
+// hk_scene_edit.cpp — in-place scene edits: hk_scene_set_transform (device transform + BVH refit) and hk_scene_update_materials.
+#include "hk_host.h"
+
+// ---- in-place scene edits -----------------------------------------------------------------------------------------------------
+// Neither entry point waits for the device: the noted calls are rendered first (against the scene as it was), the lanes are joined, and
+// the work is enqueued on the context's stream behind everything already there.  Every argument is checked before anything changes.
+// Caches keyed by the scene that an edit must not invalidate, and why it does not: DScene::all_opaque and the HK_TRI_OPAQUE bits (opacity
+// class of every material and the medium interfaces are unchanged), kinds_mask (kinds unchanged), simple_lights / has_escape_lights
+// (lights and textures unchanged), bvh_depth and n_nodes (topology unchanged), the light BVH (built from the base geometry, Q18),
+// the context's noted call (flushed) and lanes (joined); the integrator's path state is sized from those flags only.
+namespace {
+// the transform of the header's arithmetic: m as given, its normal matrix in double, identity => copy
+std::string make_xform(const float* m34, DXform& X) {
+    for (int j = 0; j < 12; ++j)
+        if (!std::isfinite(m34[j])) return "hk_scene_set_transform: non-finite matrix entry";
+    std::memcpy(X.m, m34, sizeof X.m);
+    static const float id[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    X.copy = 1;
+    for (int j = 0; j < 12; ++j)
+        if (m34[j] != id[j]) X.copy = 0;
+    double A[3][3], Cf[3][3];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) A[i][j] = m34[4 * i + j];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+            Cf[i][j] = A[i1][j1] * A[i2][j2] - A[i1][j2] * A[i2][j1];
+        }
+    const double det = (A[0][0] * Cf[0][0] + A[0][1] * Cf[0][1]) + A[0][2] * Cf[0][2];
+    if (!(det != 0.0) || !std::isfinite(det)) return "hk_scene_set_transform: singular matrix";
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            X.nm[3 * i + j] = (float)(Cf[i][j] / det);
+            if (!std::isfinite(X.nm[3 * i + j])) return "hk_scene_set_transform: the normal matrix overflows";
+        }
+    return std::string();
+}
+// A grid for the quantised nodes that contains every node after the edit, without reading the device: the union over the transform
+// intervals of (identity) the base bounds of their triangle blocks, (otherwise) the 8 corners of that box through the point formula in
+// double, widened by a bound on the binary32 rounding; then one cell of margin.  false: no finite grid (the float nodes are used).
+bool quant_grid(const hk_scene* s, DQGrid& g) {
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    const int B = hk_scene::XF_BLOCK;
+    for (const auto& kv : s->xf) {
+        const int a = kv.first, e = kv.second.end;
+        double blo[3] = {INFINITY, INFINITY, INFINITY}, bhi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (int b = a / B; b <= (e - 1) / B; ++b)   // whole blocks: a superset of the interval
+            for (int k = 0; k < 3; ++k) blo[k] = std::min(blo[k], (double)s->block_box[6 * (size_t)b + k]), bhi[k] = std::max(bhi[k], (double)s->block_box[6 * (size_t)b + 3 + k]);
+        if (kv.second.identity) {
+            for (int k = 0; k < 3; ++k) lo[k] = std::min(lo[k], blo[k]), hi[k] = std::max(hi[k], bhi[k]);
+            continue;
+        }
+        const float* m = kv.second.m;
+        for (int k = 0; k < 3; ++k) {
+            double mag = std::fabs((double)m[4 * k + 3]);
+            for (int j = 0; j < 3; ++j) mag += std::fabs((double)m[4 * k + j]) * std::max(std::fabs(blo[j]), std::fabs(bhi[j]));
+            const double err = mag * std::ldexp(1.0, -20);   // >= the rounding of three products and three sums in binary32
+            for (int corner = 0; corner < 8; ++corner) {
+                double v = m[4 * k + 3];
+                for (int j = 0; j < 3; ++j) v += (double)m[4 * k + j] * ((corner >> j) & 1 ? bhi[j] : blo[j]);
+                lo[k] = std::min(lo[k], v - err), hi[k] = std::max(hi[k], v + err);
+            }
+        }
+    }
+    for (int k = 0; k < 3; ++k) {
+        const double cell = (hi[k] - lo[k]) / 65527.0;
+        if (!std::isfinite(lo[k]) || !std::isfinite(hi[k]) || !std::isfinite(cell)) return false;
+        const double l = lo[k] - cell, h = hi[k] + cell;   // one cell of margin; then the grid as hk_scene_create lays it over a box
+        g.cell[k] = (float)std::max((h - l) / 65527.0, 1e-30);
+        g.base[k] = (float)(l - 3.0 * (double)g.cell[k]);
+        if (!std::isfinite(g.base[k]) || !std::isfinite(g.cell[k])) return false;
+    }
+    return true;
+}
+}  // namespace
+
+extern "C" int32_t hk_scene_set_transform(hk_scene* s, int32_t first_tri, int32_t n_tris, const float* m34) {
+    if (!s || !m34) return fail(HK_ERR_INVALID, "hk_scene_set_transform: null argument");
+    const int T = s->d.n_tris;
+    if (T <= 0) return fail(HK_ERR_INVALID, "hk_scene_set_transform: the scene has no triangles");
+    if (first_tri < 0 || n_tris < 1 || (int64_t)first_tri + n_tris > T) return fail(HK_ERR_INVALID, "hk_scene_set_transform: triangle range outside the scene");
+    DXform X{};
+    {
+        std::string bad = make_xform(m34, X);
+        if (!bad.empty()) return fail(HK_ERR_INVALID, bad);
+    }
+    hk_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    KnobScope knobs(&c->knobs);
+    if (int e = join_lanes(c)) return e;   // noted calls render the scene as it was; the lanes finish before the stream rewrites it
+    DScene& D = s->d;
+    if (!s->have_base) {   // the arrays as created, and the leaf slot of every triangle (first edit only: an unedited scene pays nothing)
+        HIP_TRY(s->base_pos.alloc((size_t)T * 36));
+        HIP_TRY(hipMemcpyAsync(s->base_pos.p, D.positions, (size_t)T * 36, hipMemcpyDeviceToDevice, c->stream));
+        if (D.normals) {
+            HIP_TRY(s->base_nrm.alloc((size_t)T * 36));
+            HIP_TRY(hipMemcpyAsync(s->base_nrm.p, D.normals, (size_t)T * 36, hipMemcpyDeviceToDevice, c->stream));
+        }
+        if (D.tangents) {
+            HIP_TRY(s->base_tan.alloc((size_t)T * 36));
+            HIP_TRY(hipMemcpyAsync(s->base_tan.p, D.tangents, (size_t)T * 36, hipMemcpyDeviceToDevice, c->stream));
+        }
+        HIP_TRY(s->slot_of_prim.alloc((size_t)T * 4));
+        hk::launch_slot_of_prim(c->stream, D.leaf_tris, s->bvh_leaf_tris, s->slot_of_prim.as<int>());
+        HIP_TRY(hipGetLastError());
+        s->have_base = true;
+    }
+    hk::launch_xform_tris(c->stream, X, first_tri, n_tris, s->base_pos.as<float>(), D.normals ? s->base_nrm.as<float>() : nullptr, D.tangents ? s->base_tan.as<float>() : nullptr,
+                          s->slot_of_prim.as<int>(), s->positions.as<float>(), D.normals ? s->normals.as<float>() : nullptr, D.tangents ? s->tangents.as<float>() : nullptr,
+                          D.tri_shade ? s->tri_shade.as<float>() : nullptr, s->leaf_tris.as<float4>());
+    HIP_TRY(hipGetLastError());
+    {   // the transform of every triangle interval (the quantised grid's bookkeeping)
+        const int a = first_tri, e = first_tri + n_tris;
+        auto split = [&](int at) {
+            if (at >= T) return;
+            auto it = std::prev(s->xf.upper_bound(at));
+            if (it->first == at) return;
+            hk_scene::Xf right = it->second;
+            it->second.end = at;
+            s->xf[at] = right;
+        };
+        split(a);
+        split(e);
+        s->xf.erase(s->xf.lower_bound(a), s->xf.lower_bound(e));
+        hk_scene::Xf x{e, X.copy != 0, {}};
+        std::memcpy(x.m, m34, sizeof x.m);
+        s->xf[a] = x;
+    }
+    DQGrid grid{};
+    DQNode* qn = nullptr;
+    if (s->qnodes_built) {
+        if (quant_grid(s, grid)) {
+            qn = s->qnodes.as<DQNode>();
+            for (int k = 0; k < 3; ++k) D.q_base[k] = grid.base[k], D.q_cell[k] = grid.cell[k];
+        }
+        D.qnodes = qn;   // null: no grid is known to hold the moved tree, the traversal reads the float nodes (same hits)
+    }
+    for (int L = (int)s->level_start.size() - 2; L >= 0; --L) {   // deepest level first; nothing to do when the root is a leaf
+        hk::launch_refit_level(c->stream, s->level_start[L], s->level_start[L + 1], s->nodes.as<DNode>(), qn, grid, D.leaf_tris, D.positions);
+        HIP_TRY(hipGetLastError());
+    }
+    return HK_OK;
+}
+
+namespace {
+// what an update may change: everything but the kind, a Mix's children, and the opacity class; indices must stay in range
+std::string check_material_update(const hk_scene* s, int idx, const hk_material& old, const hk_material& m) {
+    const std::string at = "hk_scene_update_materials: material " + std::to_string(idx) + ": ";
+    if (m.kind != old.kind) return at + "the kind differs from the record it replaces";
+    if (m.kind == HK_MAT_MIX && (m.i[0] != old.i[0] || m.i[1] != old.i[1] || std::memcmp(m.mix_key, old.mix_key, sizeof m.mix_key) != 0))
+        return at + "a MixMaterial's children (i[], mix_key) cannot change";
+    for (int k = 0; k < 4; ++k)
+        if (m.rgb[k].tex >= s->n_textures) return at + "rgb texture index out of range";
+    for (int k = 0; k < 8; ++k)
+        if (m.f[k].tex >= s->n_textures) return at + "float texture index out of range";
+    if (m.kind == HK_MAT_CONDUCTOR || m.kind == HK_MAT_COATED_CONDUCTOR)
+        for (int k = 0; k < 2; ++k)
+            if (m.spectrum[k] >= s->n_spectra) return at + "spectrum index out of range";
+    if (material_alpha_tested(m) != material_alpha_tested(old)) return at + "the opacity class (Matte alpha texture / alpha < 1) cannot change";
+    return std::string();
+}
+}  // namespace
+
+extern "C" int32_t hk_scene_update_materials(hk_scene* s, int32_t first, int32_t n, const hk_material* materials) {
+    if (!s || !materials) return fail(HK_ERR_INVALID, "hk_scene_update_materials: null argument");
+    if (first < 0 || n < 1 || (int64_t)first + n > s->n_materials) return fail(HK_ERR_INVALID, "hk_scene_update_materials: material range outside the scene");
+    for (int j = 0; j < n; ++j) {
+        std::string bad = check_material_update(s, first + j, s->h_materials[first + j], materials[j]);
+        if (!bad.empty()) return fail(HK_ERR_INVALID, bad);
+    }
+    hk_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    KnobScope knobs(&c->knobs);
+    const size_t bytes = (size_t)n * sizeof(DMaterial);
+    // a pinned staging buffer whose previous copy has run (at most four; the oldest is waited for only when all four are in flight)
+    hk_scene::Staging* st = nullptr;
+    for (auto& b : s->staging)
+        if (b.bytes >= bytes && hipEventQuery(b.ev) == hipSuccess) {
+            st = &b;
+            break;
+        }
+    if (!st) {
+        if (s->staging.size() < 4) {
+            s->staging.emplace_back();
+            st = &s->staging.back();
+            HIP_TRY(hipEventCreateWithFlags(&st->ev, hipEventDisableTiming));
+        } else {
+            st = &s->staging.front();
+            HIP_TRY(hipEventSynchronize(st->ev));
+        }
+        if (st->bytes < bytes) {
+            if (st->host) HIP_TRY(hipHostFree(st->host));
+            st->host = nullptr, st->bytes = 0;
+            HIP_TRY(hipHostMalloc(&st->host, bytes, hipHostMallocDefault));
+            st->bytes = bytes;
+        }
+    }
+    if (int e = join_lanes(c)) return e;   // noted calls render the old materials; the lanes finish before the stream rewrites them
+    DMaterial* rec = static_cast<DMaterial*>(st->host);
+    for (int j = 0; j < n; ++j) bake_material(c->r2s_host, materials[j], rec[j]);
+    HIP_TRY(hipMemcpyAsync(s->materials.as<DMaterial>() + first, rec, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipEventRecord(st->ev, c->stream));
+    for (int j = 0; j < n; ++j) s->h_materials[first + j] = materials[j];
+    return HK_OK;
+}

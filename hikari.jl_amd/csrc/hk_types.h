@@ -12,7 +12,7 @@
 #include <stdint.h>
 #include <cstdlib>
 
-// Run-time knobs (hk_api.cpp): the value of HK_<name> in the table of the context whose entry point runs on this thread, or nullptr.
+// Run-time knobs (hk_ctx.cpp): the value of HK_<name> in the table of the context whose entry point runs on this thread, or nullptr.
 // The environment is read once, by hk_ctx_create; hk_ctx_set_option changes a knob afterwards.
 // The three ways a knob is read (a value that is not a number reads as 0, as atoi has it):
 namespace hk {
@@ -123,7 +123,7 @@ struct DLightNode {
     float w[3];
     float phi, cos_o, cos_e, sin_o;
     uint32_t bits;              // bit0 two_sided, bit1 is_leaf
-    uint32_t child1_or_light;   // leaf: light index, 1-based; inner node: ENTRY of its child 0 — child 1 is the next entry, the pair shares one 128-B line (sibling-pair order, hk_api.cpp)
+    uint32_t child1_or_light;   // leaf: light index, 1-based; inner node: ENTRY of its child 0 — child 1 is the next entry, the pair shares one 128-B line (sibling-pair order, hk_scene.cpp)
     uint32_t pad[2];
 };
 

@@ -1,4 +1,4 @@
-// Test double of librccl.so.1 for tests/test_film_reduce_ranks.py: the eight entry points hk_api.cpp resolves (the Rccl struct), with
+// Test double of librccl.so.1 for tests/test_film_reduce_ranks.py: the eight entry points hk_comm.cpp resolves (the Rccl struct), with
 // the prototypes of <rccl/rccl.h>, so that hk_film_reduce runs with 2 or 3 ranks on ONE device (real RCCL refuses two ranks per GPU).
 // Ranks are processes that share a file under $FAKE_RCCL_DIR (mmap MAP_SHARED; the unique id names the file, every rank resolves the
 // name in its own $FAKE_RCCL_DIR, so the directory may be of any length); the library finds the double first because the test

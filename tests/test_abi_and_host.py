@@ -249,11 +249,11 @@ def test_bvh_builder_invariants(n_tris):
 
 
 def test_knob_names_read_equal_knob_names_listed():
-    """KNOB_NAMES (hk_api.cpp) is the list of record: hk_ctx_create copies exactly these from the environment and the option calls refuse
+    """KNOB_NAMES (hk_ctx.cpp) is the list of record: hk_ctx_create copies exactly these from the environment and the option calls refuse
     every other name.  Every "HK_..." name the sources hand to hk::knob or to a typed reader (knob_on / knob_int / knob_int_in, hk_types.h)
     must be on it — a name that is read but not listed can never be set — and every listed name must be read somewhere."""
     csrc = os.path.join(ROOT, "hikari.jl_amd", "csrc")
-    api = open(os.path.join(csrc, "hk_api.cpp")).read()
+    api = open(os.path.join(csrc, "hk_ctx.cpp")).read()   # KNOB_NAMES and both option calls live there
     listed = re.search(r"KNOB_NAMES\[\]\s*=\s*\{(.*?)\};", api, re.S)
     assert listed, "KNOB_NAMES not found"
     names = re.findall(r'"(HK_[A-Z0-9_]+)"', listed.group(1))

@@ -1,4 +1,4 @@
-"""hk_film_reduce with 2 and 3 ranks (include/hikari_mi355x.h, the "Multi-GPU behind the C-ABI" block of hk_api.cpp).
+"""hk_film_reduce with 2 and 3 ranks (include/hikari_mi355x.h, the "Multi-GPU behind the C-ABI" block of hk_comm.cpp).
 
 Real RCCL puts one rank per device and the test box has one GPU, so the ranks here talk through a test double of librccl.so.1
 (tests/native/fake_rccl.cpp): host-only, built into a directory of the test's own, found first by the library's dlopen because the
@@ -22,7 +22,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DOUBLE_SRC = os.path.join(ROOT, "tests", "native", "fake_rccl.cpp")
 WORKER = os.path.join(ROOT, "tests", "film_reduce_worker.py")
-HK_API = os.path.join(ROOT, "hikari.jl_amd", "csrc", "hk_api.cpp")
+HK_COMM_SRC = os.path.join(ROOT, "hikari.jl_amd", "csrc", "hk_comm.cpp")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 W, H = 67, 45                   # tests/film_reduce_worker.py
 COUNT = 4 * W * H               # [rgb 3N | weight N]
@@ -73,7 +73,7 @@ def test_double_builds_warning_free(tmp_path):
 
 
 def test_double_exports_exactly_what_the_library_resolves(double_dir):
-    with open(HK_API) as f:
+    with open(HK_COMM_SRC) as f:
         wanted = set(re.findall(r'\bsym\("(\w+)"\)', f.read()))
     assert len(wanted) == 8, wanted
     r = subprocess.run(["nm", "-D", "--defined-only", os.path.join(double_dir, "librccl.so.1")], capture_output=True, text=True, check=True)

@@ -670,7 +670,7 @@ def test_full_size_properties(hk):
     assert np.allclose(w, w[0], rtol=1e-2) and w[0] > 0
     st = vp.stats()
     assert st.rays_closest >= 4 * 640000
-    # a pass this size of a small closed scene takes the static stride on one stream (hk_api.cpp ensure_state, "mid"); the tickets and
+    # a pass this size of a small closed scene takes the static stride on one stream (hk_render.cpp ensure_state, "mid"); the tickets and
     # the second stream of a full-size pass must give the same film, bit for bit
     with hk.Context.get(0).options(HK_MID_PASS_PATHS_M=0):
         vp(s, film, cam)

@@ -9,8 +9,13 @@ cd "$ROOT/hikari.jl_amd/csrc"
 mkdir -p "$ROOT/build"
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -I../../include"
 /opt/rocm/bin/hipcc $F "$@" -c hk_kernels.hip -o /tmp/hk_kernels_$name.o &
-/opt/rocm/bin/hipcc $F "$@" -x hip -c hk_api.cpp -o /tmp/hk_api_$name.o &
+HOST="hk_ctx hk_scene hk_scene_edit hk_film hk_render hk_test_api hk_comm"   # (the flags reach DStats and the structs of hk_host.h: every host file is rebuilt)
+host_objs=""
+for f in $HOST; do
+    /opt/rocm/bin/hipcc $F "$@" -x hip -c $f.cpp -o /tmp/${f}_$name.o &
+    host_objs="$host_objs /tmp/${f}_$name.o"
+done
 wait
 make -s bvh_build.o light_bvh.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$ROOT/build/lib_$name.so" /tmp/hk_kernels_$name.o /tmp/hk_api_$name.o bvh_build.o light_bvh.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$ROOT/build/lib_$name.so" /tmp/hk_kernels_$name.o $host_objs bvh_build.o light_bvh.o
 echo "$ROOT/build/lib_$name.so"
