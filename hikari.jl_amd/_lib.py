@@ -72,6 +72,10 @@ def lib():
         "hk_postprocess": ([vp, C.POINTER(A.hk_postprocess_params), i32, i32, PF, PF, PF], i32),
         "hk_denoise": ([vp, C.POINTER(A.hk_denoise_params), i32, i32, PF, PF, PF, PF, PF], i32),
         "hk_film_fill_aux": ([vp, vp, C.POINTER(A.hk_camera), i32, i32, i32, PF, PF, PF], i32),
+        "hk_film_update_aux": ([vp, vp, vp, C.POINTER(A.hk_camera), i32], i32),
+        "hk_film_read_aux": ([vp, vp, PF, PF, PF], i32),
+        "hk_film_present": ([vp, vp, C.POINTER(A.hk_denoise_params), C.POINTER(A.hk_postprocess_params), PF], i32),
+        "hk_film_present_async": ([vp, vp, C.POINTER(A.hk_denoise_params), C.POINTER(A.hk_postprocess_params)], i32),
         "hk_test_light": ([vp, vp, i32, i32, i32, PF, PF, PF, PF], i32),
         "hk_test_bsdf": ([vp, vp, i32, i32, i32, i32, PF, PF, PF, PF, PF, PF, PF], i32),
         "hk_test_mix": ([vp, vp, i32, i32, PF, PF, PF, PI], i32),

@@ -58,15 +58,64 @@ extern "C" int32_t hk_film_read_accum(hk_ctx* c, hk_film* f, void* out) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     return HK_OK;
 }
+// hk_film_present's chain (the entry points and what they promise: the end of this file): K13 -> variance -> a-trous passes -> postprocess
+// into `readback`, on packed buffers of the film.
+namespace {
+struct PresentJob {   // hk_film_present: what fills `readback` in place of the plain K13 (checked by check_present)
+    const hk_denoise_params* dn;
+    const hk_postprocess_params* pp;
+};
+// the refusals of both forms; nothing is enqueued before every one of them has passed
+int check_present(hk_ctx* c, hk_film* f, const hk_denoise_params* dn, const hk_postprocess_params* pp) {
+    if (!c || !f) return fail(HK_ERR_INVALID, "hk_film_present: null argument");
+    if (f->ctx != c) return fail(HK_ERR_INVALID, "hk_film_present: film belongs to another context");
+    if (dn && (dn->iterations < 0 || dn->iterations > 30)) return fail(HK_ERR_INVALID, "hk_film_present: iterations out of range");
+    if (pp && (pp->tonemap < HK_TONEMAP_NONE || pp->tonemap > HK_TONEMAP_FILMIC)) return fail(HK_ERR_INVALID, "hk_film_present: unknown tonemap");
+    if (dn && !f->have_aux) return fail(HK_ERR_INVALID, "hk_film_present: denoising needs hk_film_update_aux first");
+    if (pp && pp->mask_escaped && !f->have_aux) return fail(HK_ERR_INVALID, "hk_film_present: the escaped mask needs hk_film_update_aux first");
+    return HK_OK;
+}
+int enqueue_present_chain(hk_ctx* c, hk_film* f, const PresentJob& job) {
+    const int w = f->width, h = f->height;
+    const size_t n = (size_t)w * h;
+    const int iterations = job.dn ? job.dn->iterations : 0;
+    float* out = f->readback.as<float>();
+    if (iterations == 0 && !job.pp) {   // linear and unfiltered: hk_film_read_rgb's frame
+        hk::launch_finalize(c->stream, f->accum, f->f64, out, w, h);
+        return HK_OK;
+    }
+    if (f->frame[0].bytes != n * 16) HIP_TRY(f->frame[0].alloc(n * 16));
+    if (iterations > 0 && f->frame[1].bytes != n * 16) HIP_TRY(f->frame[1].alloc(n * 16));
+    if (iterations > 0 && f->variance.bytes != n * 4) HIP_TRY(f->variance.alloc(n * 4));
+    const float4* guides = f->have_aux ? f->guides.as<float4>() : nullptr;
+    hk::launch_present_prepare(c->stream, f->accum, f->f64, f->frame[0].as<float4>(), w, h);
+    if (iterations == 0) {
+        hk::launch_present_post(c->stream, *job.pp, f->frame[0].as<float4>(), guides, out, h, w);
+        return HK_OK;
+    }
+    if (job.dn->use_variance) hk::launch_present_variance(c->stream, f->frame[0].as<float4>(), f->variance.as<float>(), h, w);
+    for (int i = 1; i <= iterations; ++i) {   // odd passes ping -> pong, even passes back (hk_denoise); the last one writes the output frame
+        const bool last = i == iterations;
+        hk::launch_present_atrous(c->stream, *job.dn, 1 << (i - 1), f->frame[(i & 1) ^ 1].as<float4>(), guides, f->variance.as<float>(), last ? nullptr : f->frame[i & 1].as<float4>(),
+                                  last ? out : nullptr, job.pp, h, w);
+    }
+    return HK_OK;
+}
+}  // namespace
 // K13 + the device-to-host copy of the frame.  A pageable destination made this the most expensive part of an interactive viewer's loop
 // (round 4: 3.7 ms of a 5.3-ms one-sample call at 800^2 — the runtime stages a pageable copy through small pinned buffers and the
 // stream waits for each).  Now the frame lands in PINNED memory: the film's own staging buffers (two, in turn), or the caller's
 // buffer itself once the same pointer has come twice in a row and hipHostRegister accepted it (a viewer reads into ONE framebuffer).
-static int enqueue_frame_read(hk_ctx* c, hk_film* f, float* direct) {
+static int enqueue_frame_read(hk_ctx* c, hk_film* f, float* direct, const PresentJob* job) {   // job == nullptr: the plain frame
     const size_t bytes = (size_t)3 * f->width * f->height * 4;
     if (int e = join_lanes(c)) return e;
     if (f->readback.bytes != bytes) HIP_TRY(f->readback.alloc(bytes));
     if (!f->ev_read) HIP_TRY(hipEventCreateWithFlags(&f->ev_read, hipEventDisableTiming));
+    if (job) {
+        if (int e = enqueue_present_chain(c, f, *job)) return e;
+    } else
+        hk::launch_finalize(c->stream, f->accum, f->f64, f->readback.as<float>(), f->width, f->height);
+    HIP_TRY(hipGetLastError());
     float* dst = direct;
     if (!dst) {
         const int k = f->staging_next;
@@ -75,8 +124,6 @@ static int enqueue_frame_read(hk_ctx* c, hk_film* f, float* direct) {
         f->staging_last = k;
         f->staging_next = k ^ 1;
     }
-    hk::launch_finalize(c->stream, f->accum, f->f64, f->readback.as<float>(), f->width, f->height);
-    HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(dst, f->readback.p, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipEventRecord(f->ev_read, c->stream));
     return HK_OK;
@@ -109,7 +156,7 @@ extern "C" int32_t hk_film_read_rgb(hk_ctx* c, hk_film* f, float* out) {
     }
     f->last_out = out;
     const bool direct = f->pinned_user == out;
-    if (int e = enqueue_frame_read(c, f, direct ? out : nullptr)) return e;
+    if (int e = enqueue_frame_read(c, f, direct ? out : nullptr, nullptr)) return e;
     HIP_TRY(hipEventSynchronize(f->ev_read));
     if (!direct) std::memcpy(out, f->staging[f->staging_last], bytes);
     return HK_OK;
@@ -148,7 +195,7 @@ extern "C" int32_t hk_film_read_rgb_async(hk_ctx* c, hk_film* f) {
     HIP_TRY(hipSetDevice(c->device));
     KnobScope knobs(&c->knobs);
     if (f->read_in_flight) HIP_TRY(hipEventSynchronize(f->ev_read));   // (two buffers: the one about to be refilled is the one BEFORE the last)
-    if (int e = enqueue_frame_read(c, f, nullptr)) return e;
+    if (int e = enqueue_frame_read(c, f, nullptr, nullptr)) return e;
     f->read_in_flight = true;
     return HK_OK;
 }
@@ -238,5 +285,74 @@ extern "C" int32_t hk_film_fill_aux(hk_ctx* c, hk_scene* sc, const hk_camera* ca
     HIP_TRY(hipMemcpyAsync(normal, dn.p, n * 12, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(depth, dd.p, n * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return HK_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// THE DISPLAY CHAIN ON THE DEVICE.  fill_aux_buffers!, denoise! and postprocess! of the reference work on the film's own device arrays
+// (film.jl:410-483, denoise.jl:301-376, postprocess.jl:293-357); so do these: hk_film_update_aux keeps the guides in buffers of the
+// film, hk_film_present runs K13 -> variance -> a-trous passes -> postprocess on packed buffers of the film and copies ONE frame to the
+// host, through the pinned staging buffers of hk_film_read_rgb.  The arithmetic is that of hk_film_read_rgb -> hk_denoise ->
+// hk_postprocess, bit for bit.
+// ---------------------------------------------------------------------------------------------------
+extern "C" int32_t hk_film_update_aux(hk_ctx* c, hk_film* f, hk_scene* sc, const hk_camera* cam, int32_t has_infinite_lights) {
+    if (!c || !f || !sc || !cam) return fail(HK_ERR_INVALID, "hk_film_update_aux: null argument");
+    if (f->ctx != c) return fail(HK_ERR_INVALID, "hk_film_update_aux: film belongs to another context");
+    if (sc->ctx != c) return fail(HK_ERR_INVALID, "hk_film_update_aux: scene belongs to another context");
+    HIP_TRY(hipSetDevice(c->device));
+    KnobScope knobs(&c->knobs);
+    if (int e = join_lanes(c)) return e;
+    const size_t n = (size_t)f->width * f->height;
+    if (f->guides.bytes != n * 16) HIP_TRY(f->guides.alloc(n * 16));
+    if (f->albedo.bytes != n * 12) HIP_TRY(f->albedo.alloc(n * 12));
+    hk::launch_aux_packed(c->stream, sc->d, make_camera(*cam), f->height, f->width, has_infinite_lights ? 1e30f : INFINITY, f->albedo.as<float>(), f->guides.as<float4>());
+    HIP_TRY(hipGetLastError());
+    f->have_aux = true;
+    return HK_OK;
+}
+extern "C" int32_t hk_film_read_aux(hk_ctx* c, hk_film* f, float* albedo, float* normal, float* depth) {
+    if (!c || !f) return fail(HK_ERR_INVALID, "hk_film_read_aux: null argument");
+    if (f->ctx != c) return fail(HK_ERR_INVALID, "hk_film_read_aux: film belongs to another context");
+    if (!f->have_aux) return fail(HK_ERR_INVALID, "hk_film_read_aux before hk_film_update_aux");
+    HIP_TRY(hipSetDevice(c->device));
+    if (int e = join_lanes(c)) return e;
+    const size_t n = (size_t)f->width * f->height;
+    std::vector<float> packed;
+    if (normal || depth) {
+        packed.resize(4 * n);
+        HIP_TRY(hipMemcpyAsync(packed.data(), f->guides.p, n * 16, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (albedo) HIP_TRY(hipMemcpyAsync(albedo, f->albedo.p, n * 12, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < n && (normal || depth); ++i) {
+        if (normal) normal[3 * i] = packed[4 * i], normal[3 * i + 1] = packed[4 * i + 1], normal[3 * i + 2] = packed[4 * i + 2];
+        if (depth) depth[i] = packed[4 * i + 3];
+    }
+    return HK_OK;
+}
+extern "C" int32_t hk_film_present(hk_ctx* c, hk_film* f, const hk_denoise_params* dn, const hk_postprocess_params* pp, float* out) {
+    if (int e = check_present(c, f, dn, pp)) return e;
+    if (!out) return fail(HK_ERR_INVALID, "hk_film_present: out_hw3 is null");
+    HIP_TRY(hipSetDevice(c->device));
+    KnobScope knobs(&c->knobs);
+    if (f->read_in_flight) {   // an asynchronous read nobody waited for: its staging buffer is simply overtaken
+        HIP_TRY(hipEventSynchronize(f->ev_read));
+        f->read_in_flight = false;
+    }
+    const bool direct = f->pinned_user == out;   // (hk_film_pin_host named this buffer)
+    const PresentJob job{dn, pp};
+    if (int e = enqueue_frame_read(c, f, direct ? out : nullptr, &job)) return e;
+    HIP_TRY(hipEventSynchronize(f->ev_read));
+    if (!direct) std::memcpy(out, f->staging[f->staging_last], (size_t)3 * f->width * f->height * 4);
+    return HK_OK;
+}
+extern "C" int32_t hk_film_present_async(hk_ctx* c, hk_film* f, const hk_denoise_params* dn, const hk_postprocess_params* pp) {
+    if (int e = check_present(c, f, dn, pp)) return e;
+    HIP_TRY(hipSetDevice(c->device));
+    KnobScope knobs(&c->knobs);
+    if (f->read_in_flight) HIP_TRY(hipEventSynchronize(f->ev_read));   // (two buffers: the one about to be refilled is the one BEFORE the last)
+    const PresentJob job{dn, pp};
+    if (int e = enqueue_frame_read(c, f, nullptr, &job)) return e;
+    f->read_in_flight = true;
     return HK_OK;
 }

@@ -308,6 +308,12 @@ struct hk_film {
     void* pinned_user = nullptr;    // ... registered with the driver (hipHostRegister) — the copy goes there directly
     bool pinned_explicit = false;   // registered by hk_film_pin_host (stays until hk_film_unpin_host / hk_film_destroy)
     void* pin_failed = nullptr;     // HK_READBACK_PIN=1: the pointer whose registration the driver refused (not retried every frame)
+    // hk_film_update_aux / hk_film_present: the display chain's device buffers, packed one float4 per pixel in Julia [h,w] order.  Sized
+    // once per film (aux on the first update, the rest on the first present) and reused: a steady-state present allocates nothing.
+    // The chain's 3-float output frame is `readback`.
+    DevBuf guides, albedo;          // (nx, ny, nz, depth) and film.albedo (3 floats per pixel)
+    DevBuf frame[2], variance;      // (r, g, b, lum) ping and pong, 3x3 luminance variance of the pass-0 frame
+    bool have_aux = false;          // hk_film_update_aux has run
 };
 
 struct hk_integrator {

@@ -43,6 +43,12 @@ void launch_aux(hipStream_t s, const DScene& sc, const DCamera& cam, int h, int 
 void launch_postprocess(hipStream_t s, const hk_postprocess_params& P, const float* src, const float* depth, float* dst, int h, int w);
 void launch_denoise_variance(hipStream_t s, const float* src, float* variance, int h, int w);
 void launch_denoise_atrous(hipStream_t s, const hk_denoise_params& P, int step, const float* src, const float* normal, const float* depth, const float* variance, float* dst, int h, int w);
+void launch_aux_packed(hipStream_t s, const DScene& sc, const DCamera& cam, int h, int w, float miss_depth, float* albedo, float4* guides);
+void launch_present_prepare(hipStream_t s, const void* accum, bool f64, float4* frame, int w, int h);
+void launch_present_variance(hipStream_t s, const float4* frame, float* variance, int h, int w);
+void launch_present_post(hipStream_t s, const hk_postprocess_params& PP, const float4* frame, const float4* guides, float* out, int h, int w);
+void launch_present_atrous(hipStream_t s, const hk_denoise_params& P, int step, const float4* frame, const float4* guides, const float* variance, float4* dst, float* out,
+                           const hk_postprocess_params* pp, int h, int w);
 void launch_slot_of_prim(hipStream_t s, const float4* leaf, int n, int* slot_of_prim);
 void launch_xform_tris(hipStream_t s, const DXform& X, int first, int n, const float* bp, const float* bn, const float* bt, const int* slot_of_prim, float* pos, float* nrm, float* tan, float* shade,
                        float4* leaf);

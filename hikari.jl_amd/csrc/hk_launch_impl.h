@@ -386,6 +386,31 @@ void launch_denoise_atrous(hipStream_t s, const hk_denoise_params& P, int step, 
                            float* dst, int h, int w) {
     hipLaunchKernelGGL(k_denoise_atrous, dim3(grid_for(h * w, 256, 8192)), dim3(256), 0, s, P, step, src, normal, depth, variance, dst, h, w);
 }
+// ---- present: the display chain on the film's own packed buffers ----
+void launch_aux_packed(hipStream_t s, const DScene& sc, const DCamera& cam, int h, int w, float miss_depth, float* albedo, float4* guides) {
+    hipLaunchKernelGGL(k_aux_packed, dim3(grid_for(h * w, HK_TRACE_BLOCK, 2048)), dim3(HK_TRACE_BLOCK), 0, s, sc, cam, h, w, miss_depth, albedo, guides);
+}
+void launch_present_prepare(hipStream_t s, const void* accum, bool f64, float4* frame, int w, int h) {
+    int g = grid_for(w * h, 256, 4096);
+    if (f64)
+        hipLaunchKernelGGL(k_present_prepare<double>, dim3(g), dim3(256), 0, s, (const double*)accum, frame, w, h);
+    else
+        hipLaunchKernelGGL(k_present_prepare<float>, dim3(g), dim3(256), 0, s, (const float*)accum, frame, w, h);
+}
+void launch_present_variance(hipStream_t s, const float4* frame, float* variance, int h, int w) {
+    hipLaunchKernelGGL(k_present_variance, dim3(grid_for(h * w, 256, 8192)), dim3(256), 0, s, frame, variance, h, w);
+}
+void launch_present_post(hipStream_t s, const hk_postprocess_params& PP, const float4* frame, const float4* guides, float* out, int h, int w) {
+    hipLaunchKernelGGL(k_present_post, dim3(grid_for(h * w, 256, 8192)), dim3(256), 0, s, PP, frame, guides, out, h, w);
+}
+// one a-trous pass; out != nullptr: the LAST pass (pp != nullptr: with the postprocess), else frame -> dst
+void launch_present_atrous(hipStream_t s, const hk_denoise_params& P, int step, const float4* frame, const float4* guides, const float* variance, float4* dst, float* out,
+                           const hk_postprocess_params* pp, int h, int w) {
+    const hk_postprocess_params PP = pp ? *pp : hk_postprocess_params{};
+    with_bool(out != nullptr, [&](auto FINAL) {
+        hipLaunchKernelGGL(k_present_atrous<decltype(FINAL)::value>, dim3(grid_for(h * w, 256, 8192)), dim3(256), 0, s, P, PP, pp ? 1 : 0, step, frame, guides, variance, dst, out, h, w);
+    });
+}
 void launch_slot_of_prim(hipStream_t s, const float4* leaf, int n, int* slot_of_prim) {
     hipLaunchKernelGGL(k_slot_of_prim, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, leaf, n, slot_of_prim);
 }

@@ -189,7 +189,7 @@ class VolPath:
         self._external_accum = None
         self._readback = None  # the one host buffer hk_film_read_rgb fills (a stable pointer: read_framebuffer(view=True) pins it)
         self._pinned = None    # the film handle `_readback` is registered with (hk_film_pin_host)
-        self._read_pending = False
+        self._read_pending = False      # an asynchronous read nobody has waited for yet: False, or the Film attribute its frame belongs to
 
     # -- lazily created device state (the reference's `vp.state`, volpath.jl:463-482) --
     def _ensure(self, film):
@@ -237,10 +237,9 @@ class VolPath:
             # the frame an interactive viewer shows, one call behind: this call's samples are handed to the GPU, the frame of the PREVIOUS
             # call (its copy was enqueued then) is waited for while they render, then this call's copy is enqueued behind them
             _lib.check(L.hk_flush(self._ctx.h), "hk_flush")
-            if self._read_pending:
-                self._frame_from_pinned(film)
+            self._collect_pending(film)
             _lib.check(L.hk_film_read_rgb_async(self._ctx.h, self._film[0]), "hk_film_read_rgb_async")
-            self._read_pending = True
+            self._read_pending = "framebuffer"
         elif readback:
             self.read_framebuffer(film, view=(readback == "view"))
 
@@ -271,6 +270,14 @@ class VolPath:
                 film.framebuffer = np.empty((film.height, film.width, 3), dtype=np.float32)
             film.framebuffer[...] = np.transpose(rb, (1, 0, 2))
 
+    def _collect_pending(self, film):
+        """The film has ONE pair of staging buffers and one read in flight, a raw frame (readback="pipelined") or a presented one
+        (present(pipelined=True)): whichever it is, it is waited for and goes to the buffer it belongs to."""
+        if self._read_pending == "postprocess_buffer":
+            self._present_from_pinned(film)
+        elif self._read_pending:
+            self._frame_from_pinned(film)
+
     def _frame_from_pinned(self, film):
         """hk_film_read_wait: film.framebuffer becomes a view of the film's pinned staging buffer holding the last asynchronous read"""
         ptr = A.PF()
@@ -282,8 +289,63 @@ class VolPath:
     def finish_pipelined(self, film):
         """after a loop of render_samples(..., readback="pipelined"): the frame of the LAST call"""
         if self._read_pending:
-            self._frame_from_pinned(film)
-            film.framebuffer = film.framebuffer.copy()      # (the pinned buffer belongs to the film)
+            raw = self._read_pending == "framebuffer"
+            self._collect_pending(film)
+            if raw:
+                film.framebuffer = film.framebuffer.copy()      # (the pinned buffer belongs to the film)
+
+    # -- the display chain on the device (hk_film_update_aux / hk_film_present) --
+    def update_aux(self, scene, film, camera, has_infinite_lights=False, host_copy=False):
+        """fill_aux_buffers! kept on the device: the guides of `present` go into buffers the library's film owns.  Call it again after a
+        scene transform or a camera change.  host_copy=True also fills film.albedo / normal / depth (hk_film_read_aux)."""
+        self._ensure(film)
+        L = _lib.lib()
+        cam = camera.record()
+        _lib.check(L.hk_film_update_aux(self._ctx.h, self._film[0], scene_handle(self._ctx, scene), C.byref(cam), 1 if has_infinite_lights else 0), "hk_film_update_aux")
+        if host_copy:
+            w, h = film.width, film.height
+            a, n, d = np.empty((w, h, 3), np.float32), np.empty((w, h, 3), np.float32), np.empty((w, h), np.float32)
+            _lib.check(L.hk_film_read_aux(self._ctx.h, self._film[0], a.ctypes.data_as(A.PF), n.ctypes.data_as(A.PF), d.ctypes.data_as(A.PF)), "hk_film_read_aux")
+            film.albedo, film.normal, film.depth = np.transpose(a, (1, 0, 2)).copy(), np.transpose(n, (1, 0, 2)).copy(), np.transpose(d, (1, 0)).copy()
+        return film
+
+    def present(self, film, denoise=None, pipelined=False, **postprocess_kwargs):
+        """The frame a viewer shows: K13 -> [denoise] -> [postprocess] on the device and one copy to the host (hk_film_present); writes and
+        returns film.postprocess_buffer.  denoise: None, True (DenoiseConfig()) or a DenoiseConfig — needs update_aux first.
+        postprocess_kwargs: those of Film.postprocess (exposure, tonemap, gamma, white_point, sensor, background); none = linear output.
+        pipelined=True enqueues this frame (hk_film_present_async) and returns the frame of the PREVIOUS pipelined call, like
+        render_samples(readback="pipelined"); finish_present brings the last one."""
+        from .denoise import DenoiseConfig
+        from .postprocess import make_params
+        self._ensure(film)
+        L = _lib.lib()
+        dn = None if denoise is None or denoise is False else (DenoiseConfig() if denoise is True else denoise).record()
+        pp = make_params(**postprocess_kwargs) if postprocess_kwargs else None
+        dn_ref, pp_ref = (C.byref(dn) if dn is not None else None), (C.byref(pp) if pp is not None else None)
+        if pipelined:
+            _lib.check(L.hk_flush(self._ctx.h), "hk_flush")
+            self._collect_pending(film)
+            _lib.check(L.hk_film_present_async(self._ctx.h, self._film[0], dn_ref, pp_ref), "hk_film_present_async")
+            self._read_pending = "postprocess_buffer"
+            return film.postprocess_buffer
+        self._read_pending = False          # (the library lets a synchronous call overtake a read nobody waited for)
+        out = np.empty((film.width, film.height, 3), dtype=np.float32)
+        _lib.check(L.hk_film_present(self._ctx.h, self._film[0], dn_ref, pp_ref, out.ctypes.data_as(A.PF)), "hk_film_present")
+        film.postprocess_buffer = np.transpose(out, (1, 0, 2)).copy()
+        return film.postprocess_buffer
+
+    def _present_from_pinned(self, film):
+        ptr = A.PF()
+        _lib.check(_lib.lib().hk_film_read_wait(self._ctx.h, self._film[0], None, C.byref(ptr)), "hk_film_read_wait")
+        frame = np.ctypeslib.as_array(ptr, shape=(film.width, film.height, 3))
+        film.postprocess_buffer = np.transpose(frame, (1, 0, 2)).copy()      # (the pinned buffer belongs to the film)
+        self._read_pending = False
+
+    def finish_present(self, film):
+        """after a loop of present(..., pipelined=True): the frame of the LAST call"""
+        if self._read_pending == "postprocess_buffer":
+            self._present_from_pinned(film)
+        return film.postprocess_buffer
 
     def read_accumulators(self, film):
         n = film.width * film.height

@@ -528,6 +528,30 @@ int32_t hk_denoise(hk_ctx* ctx, const hk_denoise_params* params, int32_t width, 
 int32_t hk_film_fill_aux(hk_ctx* ctx, hk_scene* scene, const hk_camera* cam, int32_t width, int32_t height, int32_t has_infinite_lights,
                          float* albedo, float* normal, float* depth);
 
+/* ---------------------------------------------------------------------------------------------
+ * The display chain on the device: what a viewer shows after every render! is the denoised, tone-mapped frame, and in the reference
+ * fill_aux_buffers!, denoise! and postprocess! all work on the film's own device arrays.  These entry points do the same; like every
+ * other film call they render the noted small calls first and work on ctx's stream.
+ *
+ * update_aux: fill_aux_buffers! kept on the device — the first-hit guides go into buffers the FILM owns (allocated on first use,
+ *   reused afterwards).  Enqueued on ctx's stream, no wait.  Valid until the next call or the film's destruction; after a scene
+ *   transform or a camera change the caller calls it again.
+ * read_aux: host copies of what update_aux computed (any pointer may be NULL); Julia [h,w] layout as the fill_aux entry point above; synchronises.
+ * present: K13 finalize -> [variance -> `iterations` a-trous passes] -> [postprocess] entirely on the device, then ONE copy of the
+ *   result (Julia [h,w] RGB{Float32}) to the host.  dn == NULL: no denoise.  pp == NULL: linear output.  Non-destructive: the
+ *   accumulators and the aux buffers are only read.  The arithmetic is that of the host chain (read_rgb -> denoise -> postprocess)
+ *   bit for bit; with neither dn nor pp the frame is the one of the plain read.  The synchronous form synchronises; the _async form
+ *   goes through the film's two pinned staging buffers exactly like the asynchronous read, and the same wait call collects it.
+ *   Every scratch buffer belongs to the film and is sized once: a steady-state present allocates nothing.
+ * HK_ERR_INVALID (nothing enqueued): a null ctx / film, a film of another context, out_hw3 == NULL in the synchronous form, dn != NULL
+ *   or pp->mask_escaped != 0 on a film that never had update_aux, dn->iterations outside 0..30, an unknown tonemap, read_aux before
+ *   update_aux.
+ * ------------------------------------------------------------------------------------------- */
+int32_t hk_film_update_aux(hk_ctx* ctx, hk_film* film, hk_scene* scene, const hk_camera* cam, int32_t has_infinite_lights);
+int32_t hk_film_read_aux(hk_ctx* ctx, hk_film* film, float* albedo, float* normal, float* depth);
+int32_t hk_film_present(hk_ctx* ctx, hk_film* film, const hk_denoise_params* dn, const hk_postprocess_params* pp, float* out_hw3);
+int32_t hk_film_present_async(hk_ctx* ctx, hk_film* film, const hk_denoise_params* dn, const hk_postprocess_params* pp);
+
 /* point-wise BSDFs of a scene's material `mat_idx` (material-dispatch.jl:23-53; spectral-eval.jl) at uv=(0,0):
    mode 0 = sample_bsdf_spectral(wo, ns, lambda, u, uc, regularize) -> out[10n] = wi3, f4, pdf, is_specular, eta_scale
    mode 1 = evaluate_bsdf_spectral(wo, wi, ns, lambda)              -> out[10n] = f4, pdf, 0...

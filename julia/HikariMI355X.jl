@@ -712,4 +712,74 @@ function fill_aux_buffers!(vp::MI355XVolPath, film::Hikari.Film, scene, camera; 
     nothing
 end
 
+"the kernel arguments of `postprocess_kernel!` for the keyword set of `Hikari.postprocess!` (what `postprocess!` above builds inline), for `present!`"
+function postprocess_record(; exposure::Real = 1f0, tonemap = :aces, gamma = 2.2f0, white_point::Real = 4f0, sensor = nothing, background = nothing)
+    ratio, apply_wb, wb = 1f0, Int32(0), ntuple(i -> i in (1, 5, 9) ? 1f0 : 0f0, 9)
+    if sensor !== nothing
+        ratio = Float32(sensor.exposure_time * sensor.iso / 100f0)
+        if sensor.white_balance > 0
+            apply_wb, wb = Int32(1), rowmajor3(Hikari.compute_white_balance_matrix(Float32(sensor.white_balance)))   # spectral/color.jl:522-547
+        end
+    end
+    mask, bg = background === nothing ? (Int32(0), Z3) : (Int32(1), (Float32(background.r), Float32(background.g), Float32(background.b)))
+    HkPostprocessParams(Float32(exposure), TONEMAPS[tonemap], gamma === nothing ? 1f0 : 1f0 / Float32(gamma), gamma === nothing ? 0 : 1, Float32(white_point),
+                        ratio, apply_wb, wb, mask, bg)
+end
+
+"""
+    update_aux!(vp, film, scene, camera; has_infinite_lights=false)
+
+`fill_aux_buffers!` kept on the device: the guides of `present!` go into buffers the library's film owns (`hk_film_update_aux`).
+Call it after the first `render!` (the film exists from then on) and again after a scene transform or a camera change.
+`host_copy = true` also fills `film.albedo` / `film.normal` / `film.depth`.
+"""
+function update_aux!(vp::MI355XVolPath, film::Hikari.Film, scene, camera; has_infinite_lights::Bool = false, host_copy::Bool = false)
+    ensure_ctx!(vp)
+    d = vp.devs[1]
+    d.film == C_NULL && error("update_aux!: render! into this film first")
+    if d.scene == C_NULL || vp.scene_id != objectid(scene)
+        d.scene != C_NULL && ccall((:hk_scene_destroy, LIB), Int32, (Ptr{Cvoid},), d.scene)
+        d.scene = flatten_scene(d.ctx, scene)
+        vp.scene_id = length(vp.devs) == 1 ? objectid(scene) : UInt(0)
+    end
+    cam = camera_record(camera)
+    check(ccall((:hk_film_update_aux, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{HkCamera}, Int32), d.ctx, d.film, d.scene, cam, has_infinite_lights), "hk_film_update_aux")
+    if host_copy
+        alb, nrm, dep = film.albedo, film.normal, film.depth
+        GC.@preserve alb nrm dep check(ccall((:hk_film_read_aux, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}),
+                                             d.ctx, d.film, Ptr{Float32}(pointer(alb)), Ptr{Float32}(pointer(nrm)), pointer(dep)), "hk_film_read_aux")
+    end
+    nothing
+end
+
+"""
+    present!(vp, film; denoise=nothing, pipelined=false, kwargs...)
+
+The frame a viewer shows: K13 -> [denoise] -> [postprocess] on the device and one copy into `film.postprocess` (`hk_film_present`).
+`denoise`: `nothing`, `true` (`Hikari.DenoiseConfig()`) or a `DenoiseConfig` — needs `update_aux!` first.  `kwargs` are those of
+`postprocess!`; none = linear output.  `pipelined = true` enqueues this frame and delivers the one of the previous pipelined call.
+"""
+function present!(vp::MI355XVolPath, film::Hikari.Film; denoise = nothing, pipelined::Bool = false, kwargs...)
+    d = vp.devs[1]
+    (d.ctx == C_NULL || d.film == C_NULL) && error("present!: render! into this film first")
+    config = denoise === true ? Hikari.DenoiseConfig() : (denoise === false ? nothing : denoise)
+    dn = config === nothing ? Ptr{HkDenoiseParams}(C_NULL) :
+         Ref(HkDenoiseParams(config.iterations, config.sigma_color, config.sigma_normal, config.sigma_depth, config.use_variance))
+    pp = isempty(kwargs) ? Ptr{HkPostprocessParams}(C_NULL) : Ref(postprocess_record(; kwargs...))
+    dst = film.postprocess
+    if pipelined
+        check(ccall((:hk_flush, LIB), Int32, (Ptr{Cvoid},), d.ctx), "hk_flush")
+        if vp.read_pending
+            GC.@preserve dst check(ccall((:hk_film_read_wait, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float32}, Ptr{Ptr{Float32}}), d.ctx, d.film, Ptr{Float32}(pointer(dst)), C_NULL), "hk_film_read_wait")
+        end
+        check(ccall((:hk_film_present_async, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{HkDenoiseParams}, Ptr{HkPostprocessParams}), d.ctx, d.film, dn, pp), "hk_film_present_async")
+        vp.read_pending = true
+    else
+        vp.read_pending = false
+        GC.@preserve dst check(ccall((:hk_film_present, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{HkDenoiseParams}, Ptr{HkPostprocessParams}, Ptr{Float32}),
+                                     d.ctx, d.film, dn, pp, Ptr{Float32}(pointer(dst))), "hk_film_present")
+    end
+    film.postprocess
+end
+
 end # module
