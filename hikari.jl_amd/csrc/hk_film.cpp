@@ -81,24 +81,22 @@ int enqueue_present_chain(hk_ctx* c, hk_film* f, const PresentJob& job) {
     const int iterations = job.dn ? job.dn->iterations : 0;
     float* out = f->readback.as<float>();
     if (iterations == 0 && !job.pp) {   // linear and unfiltered: hk_film_read_rgb's frame
-        hk::launch_finalize(c->stream, f->accum, f->f64, out, w, h);
+        hk::launch_finalize(c->stream, f->accum, f->f64, PlanarPixels{out, nullptr, nullptr}, w, h);
         return HK_OK;
     }
     if (f->frame[0].bytes != n * 16) HIP_TRY(f->frame[0].alloc(n * 16));
     if (iterations > 0 && f->frame[1].bytes != n * 16) HIP_TRY(f->frame[1].alloc(n * 16));
     if (iterations > 0 && f->variance.bytes != n * 4) HIP_TRY(f->variance.alloc(n * 4));
-    const float4* guides = f->have_aux ? f->guides.as<float4>() : nullptr;
-    hk::launch_present_prepare(c->stream, f->accum, f->f64, f->frame[0].as<float4>(), w, h);
+    float4* guides = f->have_aux ? f->guides.as<float4>() : nullptr;
+    const PackedPixels px[2] = {{f->frame[0].as<float4>(), guides}, {f->frame[1].as<float4>(), guides}};
+    hk::launch_finalize(c->stream, f->accum, f->f64, px[0], w, h);
     if (iterations == 0) {
-        hk::launch_present_post(c->stream, *job.pp, f->frame[0].as<float4>(), guides, out, h, w);
+        hk::launch_postprocess(c->stream, *job.pp, px[0], out, h, w);
         return HK_OK;
     }
-    if (job.dn->use_variance) hk::launch_present_variance(c->stream, f->frame[0].as<float4>(), f->variance.as<float>(), h, w);
-    for (int i = 1; i <= iterations; ++i) {   // odd passes ping -> pong, even passes back (hk_denoise); the last one writes the output frame
-        const bool last = i == iterations;
-        hk::launch_present_atrous(c->stream, *job.dn, 1 << (i - 1), f->frame[(i & 1) ^ 1].as<float4>(), guides, f->variance.as<float>(), last ? nullptr : f->frame[i & 1].as<float4>(),
-                                  last ? out : nullptr, job.pp, h, w);
-    }
+    if (job.dn->use_variance) hk::launch_variance(c->stream, px[0], f->variance.as<float>(), h, w);
+    for (int i = 1; i <= iterations; ++i)   // odd passes ping -> pong, even passes back (hk_denoise); the last one writes the output frame
+        hk::launch_atrous(c->stream, *job.dn, 1 << (i - 1), px[(i & 1) ^ 1], f->variance.as<float>(), px[i & 1], i == iterations ? out : nullptr, job.pp, h, w);
     return HK_OK;
 }
 }  // namespace
@@ -114,7 +112,7 @@ static int enqueue_frame_read(hk_ctx* c, hk_film* f, float* direct, const Presen
     if (job) {
         if (int e = enqueue_present_chain(c, f, *job)) return e;
     } else
-        hk::launch_finalize(c->stream, f->accum, f->f64, f->readback.as<float>(), f->width, f->height);
+        hk::launch_finalize(c->stream, f->accum, f->f64, PlanarPixels{f->readback.as<float>(), nullptr, nullptr}, f->width, f->height);
     HIP_TRY(hipGetLastError());
     float* dst = direct;
     if (!dst) {
@@ -128,16 +126,29 @@ static int enqueue_frame_read(hk_ctx* c, hk_film* f, float* direct, const Presen
     HIP_TRY(hipEventRecord(f->ev_read, c->stream));
     return HK_OK;
 }
+// an asynchronous read nobody waited for: its staging buffer is simply overtaken
+static int settle_pending_read(hk_film* f) {
+    if (f->read_in_flight) {
+        HIP_TRY(hipEventSynchronize(f->ev_read));
+        f->read_in_flight = false;
+    }
+    return HK_OK;
+}
+// the frame (job: hk_film_present's, else the plain K13) into `out`, now: straight into it when it is the film's registered host buffer, else through staging
+static int read_frame_now(hk_ctx* c, hk_film* f, float* out, const PresentJob* job) {
+    const bool direct = f->pinned_user == out;
+    if (int e = enqueue_frame_read(c, f, direct ? out : nullptr, job)) return e;
+    HIP_TRY(hipEventSynchronize(f->ev_read));
+    if (!direct) std::memcpy(out, f->staging[f->staging_last], (size_t)3 * f->width * f->height * 4);
+    return HK_OK;
+}
 extern "C" int32_t hk_film_read_rgb(hk_ctx* c, hk_film* f, float* out) {
     if (!c || !f || !out) return fail(HK_ERR_INVALID, "null argument");
     if (f->ctx != c) return fail(HK_ERR_INVALID, "film belongs to another context");
     HIP_TRY(hipSetDevice(c->device));
     KnobScope knobs(&c->knobs);
     const size_t bytes = (size_t)3 * f->width * f->height * 4;
-    if (f->read_in_flight) {   // an asynchronous read nobody waited for: its staging buffer is simply overtaken
-        HIP_TRY(hipEventSynchronize(f->ev_read));
-        f->read_in_flight = false;
-    }
+    if (int e = settle_pending_read(f)) return e;
     // Caller memory is registered with the driver only on request (the library cannot know when a buffer it registered by
     // itself is freed — a C host that mallocs a frame buffer per frame gets the same address back, and the copy would go through a
     // stale registration): hk_film_pin_host names the buffer, or HK_READBACK_PIN=1 brings back "the same pointer twice in a row".
@@ -155,19 +166,12 @@ extern "C" int32_t hk_film_read_rgb(hk_ctx* c, hk_film* f, float* out) {
         }
     }
     f->last_out = out;
-    const bool direct = f->pinned_user == out;
-    if (int e = enqueue_frame_read(c, f, direct ? out : nullptr, nullptr)) return e;
-    HIP_TRY(hipEventSynchronize(f->ev_read));
-    if (!direct) std::memcpy(out, f->staging[f->staging_last], bytes);
-    return HK_OK;
+    return read_frame_now(c, f, out, nullptr);
 }
 extern "C" int32_t hk_film_pin_host(hk_film* f, float* host_hw3) {
     if (!f || !host_hw3) return fail(HK_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(f->ctx->device));
-    if (f->read_in_flight) {
-        HIP_TRY(hipEventSynchronize(f->ev_read));
-        f->read_in_flight = false;
-    }
+    if (int e = settle_pending_read(f)) return e;
     if (f->pinned_user == host_hw3 && f->pinned_explicit) return HK_OK;
     if (f->pinned_user) (void)hipHostUnregister(f->pinned_user);
     f->pinned_user = nullptr, f->pinned_explicit = false;
@@ -181,10 +185,7 @@ extern "C" int32_t hk_film_pin_host(hk_film* f, float* host_hw3) {
 extern "C" int32_t hk_film_unpin_host(hk_film* f) {
     if (!f) return fail(HK_ERR_INVALID, "null film");
     HIP_TRY(hipSetDevice(f->ctx->device));
-    if (f->read_in_flight) {
-        HIP_TRY(hipEventSynchronize(f->ev_read));
-        f->read_in_flight = false;
-    }
+    if (int e = settle_pending_read(f)) return e;
     if (f->pinned_user) (void)hipHostUnregister(f->pinned_user);
     f->pinned_user = nullptr, f->pinned_explicit = false, f->last_out = nullptr;
     return HK_OK;
@@ -213,12 +214,12 @@ extern "C" int32_t hk_film_read_wait(hk_ctx* c, hk_film* f, float* out, const fl
 }
 
 namespace {
-int run_postprocess(hk_ctx* c, const hk_postprocess_params* P, int w, int h, const float* src_dev, const float* depth_host, float* dst_host, DevBuf& out) {
+int run_postprocess(hk_ctx* c, const hk_postprocess_params* P, int w, int h, float* src_dev, const float* depth_host, float* dst_host, DevBuf& out) {
     const size_t bytes = (size_t)3 * w * h * 4;
     HIP_TRY(out.alloc(bytes));
     DevBuf dd;
     if (depth_host && P->mask_escaped) HIP_TRY(dd.upload(depth_host, (size_t)w * h * 4));
-    hk::launch_postprocess(c->stream, *P, src_dev, dd.as<float>(), out.as<float>(), h, w);
+    hk::launch_postprocess(c->stream, *P, PlanarPixels{src_dev, nullptr, dd.as<float>()}, out.as<float>(), h, w);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(dst_host, out.p, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -232,7 +233,7 @@ extern "C" int32_t hk_film_postprocess(hk_ctx* c, hk_film* f, const hk_postproce
     size_t bytes = (size_t)3 * f->width * f->height * 4;
     if (int e = join_lanes(c)) return e;
     if (f->readback.bytes != bytes) HIP_TRY(f->readback.alloc(bytes));
-    hk::launch_finalize(c->stream, f->accum, f->f64, f->readback.as<float>(), f->width, f->height);
+    hk::launch_finalize(c->stream, f->accum, f->f64, PlanarPixels{f->readback.as<float>(), nullptr, nullptr}, f->width, f->height);
     DevBuf out;
     return run_postprocess(c, P, f->width, f->height, f->readback.as<float>(), depth, dst, out);
 }
@@ -257,12 +258,10 @@ extern "C" int32_t hk_denoise(hk_ctx* c, const hk_denoise_params* P, int32_t w, 
     HIP_TRY(nn.upload(normal, npx * 12));
     HIP_TRY(dd.upload(depth, npx * 4));
     HIP_TRY(var.alloc(npx * 4));
-    if (P->use_variance) hk::launch_denoise_variance(c->stream, a.as<float>(), var.as<float>(), h, w);
-    for (int i = 1; i <= P->iterations; ++i) {   // odd passes a -> b, even passes b -> a (denoise.jl:337-361)
-        const float* in = (i & 1) ? a.as<float>() : b.as<float>();
-        float* out = (i & 1) ? b.as<float>() : a.as<float>();
-        hk::launch_denoise_atrous(c->stream, *P, 1 << (i - 1), in, nn.as<float>(), dd.as<float>(), var.as<float>(), out, h, w);
-    }
+    const PlanarPixels px[2] = {{a.as<float>(), nn.as<float>(), dd.as<float>()}, {b.as<float>(), nn.as<float>(), dd.as<float>()}};
+    if (P->use_variance) hk::launch_variance(c->stream, px[0], var.as<float>(), h, w);
+    for (int i = 1; i <= P->iterations; ++i)   // odd passes a -> b, even passes b -> a (denoise.jl:337-361)
+        hk::launch_atrous(c->stream, *P, 1 << (i - 1), px[(i & 1) ^ 1], var.as<float>(), px[i & 1], h, w);
     HIP_TRY(hipGetLastError());
     // film.postprocess <- the last written buffer; with iterations == 0 that is the untouched framebuffer (:365-371)
     HIP_TRY(hipMemcpyAsync(dst, (P->iterations & 1) ? b.p : a.p, npx * 12, hipMemcpyDeviceToHost, c->stream));
@@ -279,7 +278,7 @@ extern "C" int32_t hk_film_fill_aux(hk_ctx* c, hk_scene* sc, const hk_camera* ca
     HIP_TRY(da.alloc(n * 12));
     HIP_TRY(dn.alloc(n * 12));
     HIP_TRY(dd.alloc(n * 4));
-    hk::launch_aux(c->stream, sc->d, make_camera(*cam), h, w, has_infinite_lights ? 1e30f : INFINITY, da.as<float>(), dn.as<float>(), dd.as<float>());
+    hk::launch_aux(c->stream, sc->d, make_camera(*cam), h, w, has_infinite_lights ? 1e30f : INFINITY, da.as<float>(), PlanarPixels{nullptr, dn.as<float>(), dd.as<float>()});
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(albedo, da.p, n * 12, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(normal, dn.p, n * 12, hipMemcpyDeviceToHost, c->stream));
@@ -305,7 +304,7 @@ extern "C" int32_t hk_film_update_aux(hk_ctx* c, hk_film* f, hk_scene* sc, const
     const size_t n = (size_t)f->width * f->height;
     if (f->guides.bytes != n * 16) HIP_TRY(f->guides.alloc(n * 16));
     if (f->albedo.bytes != n * 12) HIP_TRY(f->albedo.alloc(n * 12));
-    hk::launch_aux_packed(c->stream, sc->d, make_camera(*cam), f->height, f->width, has_infinite_lights ? 1e30f : INFINITY, f->albedo.as<float>(), f->guides.as<float4>());
+    hk::launch_aux(c->stream, sc->d, make_camera(*cam), f->height, f->width, has_infinite_lights ? 1e30f : INFINITY, f->albedo.as<float>(), PackedPixels{nullptr, f->guides.as<float4>()});
     HIP_TRY(hipGetLastError());
     f->have_aux = true;
     return HK_OK;
@@ -335,16 +334,9 @@ extern "C" int32_t hk_film_present(hk_ctx* c, hk_film* f, const hk_denoise_param
     if (!out) return fail(HK_ERR_INVALID, "hk_film_present: out_hw3 is null");
     HIP_TRY(hipSetDevice(c->device));
     KnobScope knobs(&c->knobs);
-    if (f->read_in_flight) {   // an asynchronous read nobody waited for: its staging buffer is simply overtaken
-        HIP_TRY(hipEventSynchronize(f->ev_read));
-        f->read_in_flight = false;
-    }
-    const bool direct = f->pinned_user == out;   // (hk_film_pin_host named this buffer)
+    if (int e = settle_pending_read(f)) return e;
     const PresentJob job{dn, pp};
-    if (int e = enqueue_frame_read(c, f, direct ? out : nullptr, &job)) return e;
-    HIP_TRY(hipEventSynchronize(f->ev_read));
-    if (!direct) std::memcpy(out, f->staging[f->staging_last], (size_t)3 * f->width * f->height * 4);
-    return HK_OK;
+    return read_frame_now(c, f, out, &job);
 }
 extern "C" int32_t hk_film_present_async(hk_ctx* c, hk_film* f, const hk_denoise_params* dn, const hk_postprocess_params* pp) {
     if (int e = check_present(c, f, dn, pp)) return e;

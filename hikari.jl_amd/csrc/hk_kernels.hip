@@ -4592,386 +4592,7 @@ __global__ void __launch_bounds__(256) k_film(DPathState st, DFrame fr, DTables 
     for (int tile = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)); tile < n_tiles; tile += n_waves) film_tile<ACC>(st, fr, T, accum, mine, tile);
 }
 
-// K13 (volpath.jl:384-417): out = Julia Matrix{RGB{Float32}}[height,width] column-major
-template <typename ACC>
-__global__ void k_finalize(const ACC* __restrict__ accum, float* __restrict__ out, int width, int height) {
-    size_t N = (size_t)width * height;
-    for (size_t p = blockIdx.x * (size_t)blockDim.x + threadIdx.x; p < N; p += (size_t)gridDim.x * blockDim.x) {
-        int px = (int)(p % width), py = (int)(p / width);
-        ACC w = accum[3 * N + p];
-        float r = 0.0f, g = 0.0f, b = 0.0f;
-        if (w > (ACC)0) {
-            ACC inv = (ACC)1 / w;
-            r = (float)(accum[3 * p] * inv);
-            g = (float)(accum[3 * p + 1] * inv);
-            b = (float)(accum[3 * p + 2] * inv);
-        }
-        float* o = out + 3 * ((size_t)py + (size_t)height * px);
-        o[0] = r;
-        o[1] = g;
-        o[2] = b;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// postprocess_kernel! (src/postprocess.jl:185-250): exposure, white balance, imaging ratio, tone curve, gamma, escaped-ray mask.
-// src/dst: Julia [h,w] RGB layout (3 floats per pixel, linear index i = row + h*col); depth likewise.
-// ---------------------------------------------------------------------------------------------------
-HKD float pp_unch2(float x) {
-    const float A = 0.15f, B = 0.50f, C = 0.10f, D = 0.20f, E = 0.02f, F = 0.30f;
-    return ((x * (A * x + C * B) + D * E) / (x * (A * x + B) + D * F)) - E / F;
-}
-HKD float pp_filmic(float x) {
-    x = maxf(0.0f, x - 0.004f);
-    return (x * (6.2f * x + 0.5f)) / (x * (6.2f * x + 1.7f) + 0.06f);
-}
-__global__ void __launch_bounds__(256) k_postprocess(hk_postprocess_params P, const float* __restrict__ src, const float* __restrict__ depth, float* __restrict__ dst, int h, int w) {
-    const long n = (long)h * w;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        float r = src[3 * i] * P.exposure, g = src[3 * i + 1] * P.exposure, b = src[3 * i + 2] * P.exposure;
-        if (P.apply_wb) {
-            float ro = P.wb[0] * r + P.wb[1] * g + P.wb[2] * b, go = P.wb[3] * r + P.wb[4] * g + P.wb[5] * b, bo = P.wb[6] * r + P.wb[7] * g + P.wb[8] * b;
-            r = maxf(0.0f, ro), g = maxf(0.0f, go), b = maxf(0.0f, bo);
-        }
-        r = r * P.imaging_ratio, g = g * P.imaging_ratio, b = b * P.imaging_ratio;
-        switch (P.tonemap) {
-            case HK_TONEMAP_REINHARD: {
-                float lum = 0.2126f * r + 0.7152f * g + 0.0722f * b;
-                float sc = lum > 0.0f ? 1.0f / (1.0f + lum) : 1.0f;
-                r = clampf(r * sc, 0.0f, 1.0f), g = clampf(g * sc, 0.0f, 1.0f), b = clampf(b * sc, 0.0f, 1.0f);
-            } break;
-            case HK_TONEMAP_REINHARD_EXT: {
-                float lum = 0.2126f * r + 0.7152f * g + 0.0722f * b;
-                float lw2 = P.white_point * P.white_point;
-                float sc = lum > 0.0f ? (1.0f + lum / lw2) / (1.0f + lum) : 1.0f;
-                r = clampf(r * sc, 0.0f, 1.0f), g = clampf(g * sc, 0.0f, 1.0f), b = clampf(b * sc, 0.0f, 1.0f);
-            } break;
-            case HK_TONEMAP_ACES: {
-                const float a = 2.51f, bc = 0.03f, c = 2.43f, d = 0.59f, e = 0.14f;
-                r = clampf((r * (a * r + bc)) / (r * (c * r + d) + e), 0.0f, 1.0f);
-                g = clampf((g * (a * g + bc)) / (g * (c * g + d) + e), 0.0f, 1.0f);
-                b = clampf((b * (a * b + bc)) / (b * (c * b + d) + e), 0.0f, 1.0f);
-            } break;
-            case HK_TONEMAP_UNCHARTED2: {
-                float ws = 1.0f / pp_unch2(11.2f);
-                r = clampf(pp_unch2(r * 2.0f) * ws, 0.0f, 1.0f), g = clampf(pp_unch2(g * 2.0f) * ws, 0.0f, 1.0f), b = clampf(pp_unch2(b * 2.0f) * ws, 0.0f, 1.0f);
-            } break;
-            case HK_TONEMAP_FILMIC: r = pp_filmic(r), g = pp_filmic(g), b = pp_filmic(b); break;
-            default: r = clampf(r, 0.0f, 1.0f), g = clampf(g, 0.0f, 1.0f), b = clampf(b, 0.0f, 1.0f); break;
-        }
-        if (P.apply_gamma) r = powf(r, P.inv_gamma), g = powf(g, P.inv_gamma), b = powf(b, P.inv_gamma);
-        if (P.mask_escaped && depth) {
-            int row = (int)(i % h) + 1, col = (int)(i / h) + 1;
-            int d_row = h - row + 1;  // Y flip
-            int escaped = 0, total = 0;
-            for (int dr = -1; dr <= 1; ++dr)
-                for (int dc = -1; dc <= 1; ++dc) {
-                    int nr = d_row + dr, nc = col + dc;
-                    if (nr >= 1 && nr <= h && nc >= 1 && nc <= w) {
-                        escaped += isinf(depth[(long)(nc - 1) * h + nr - 1]) ? 1 : 0;
-                        total += 1;
-                    }
-                }
-            float alpha = (float)escaped / (float)total;
-            r = r * (1.0f - alpha) + P.bg[0] * alpha, g = g * (1.0f - alpha) + P.bg[1] * alpha, b = b * (1.0f - alpha) + P.bg[2] * alpha;
-        }
-        dst[3 * i] = r, dst[3 * i + 1] = g, dst[3 * i + 2] = b;
-    }
-}
-
-// aux_buffer_kernel! (src/film.jl:435-483): first-hit albedo / normal / depth per pixel centre, Julia [h,w] layout
-__global__ void __launch_bounds__(HK_TRACE_BLOCK) k_aux(DScene sc, DCamera cam, int h, int w, float miss_depth, float* __restrict__ albedo, float* __restrict__ normal,
-                                                      float* __restrict__ depth) {
-    __shared__ int lds_stack[(HK_TRACE_BLOCK / 64) * HK_LDS_STACK * 64];
-    int* stack = lds_stack + (threadIdx.x >> 6) * (HK_LDS_STACK * 64);
-    const int lane = lane_id();
-    unsigned a = 0, b = 0;
-    const long n = (long)h * w;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        int row = (int)(i % h) + 1, col = (int)(i / h) + 1;
-        v2 pixel = mk2(((float)col - 1.0f) + 0.5f, ((float)row - 1.0f) + 0.5f);
-        v3 ro, rd;
-        float time;
-        generate_ray(cam, pixel, mk2(0.5f, 0.5f), 0.0f, ro, rd, time);
-        bool opaque;
-        HitRec hr = traverse<0, false>(sc, ro, rd, INF_F, stack, lane, a, b, opaque);
-        float alb = 0.0f, d = miss_depth;
-        v3 nn = mk3(0, 0, 0);
-        if (hr.prim >= 0) {
-            nn = geometric_normal(sc, hr.prim);
-            v3 hp = ro + rd * hr.t;
-            v3 dd = hp - ro;
-            d = sqrtf(dd.x * dd.x + dd.y * dd.y + dd.z * dd.z);
-            alb = 0.8f;
-        }
-        albedo[3 * i] = albedo[3 * i + 1] = albedo[3 * i + 2] = alb;
-        normal[3 * i] = nn.x, normal[3 * i + 1] = nn.y, normal[3 * i + 2] = nn.z;
-        depth[i] = d;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// denoise! (src/denoise.jl): 3x3 luminance variance (:236-286) and one a-trous pass (:136-229).  Buffers are Julia [h,w]
-// column-major: linear index i = (col-1)*h + (row-1), exactly the reference's idx -> (row, col) mapping.
-// ---------------------------------------------------------------------------------------------------
-HKD float denoise_luminance(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
-__global__ void __launch_bounds__(256) k_denoise_variance(const float* __restrict__ src, float* __restrict__ variance, int h, int w) {
-    const long n = (long)h * w;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        int row = (int)(i % h), col = (int)(i / h);
-        float sum = 0.0f, sum_sq = 0.0f;
-        int count = 0;
-        for (int dy = -1; dy <= 1; ++dy)
-            for (int dx = -1; dx <= 1; ++dx) {
-                int qr = row + dy, qc = col + dx;
-                if (qr >= 0 && qr < h && qc >= 0 && qc < w) {
-                    const float* q = src + 3 * ((long)qc * h + qr);
-                    float lum = denoise_luminance(q[0], q[1], q[2]);
-                    sum += lum;
-                    sum_sq += lum * lum;
-                    ++count;
-                }
-            }
-        float mean = sum / (float)count, mean_sq = sum_sq / (float)count;
-        variance[i] = maxf(0.0f, mean_sq - mean * mean);
-    }
-}
-__global__ void __launch_bounds__(256) k_denoise_atrous(hk_denoise_params P, int step, const float* __restrict__ src, const float* __restrict__ normal,
-                                                        const float* __restrict__ depth, const float* __restrict__ variance, float* __restrict__ dst, int h, int w) {
-    const float K1D[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
-    const long n = (long)h * w;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        int row = (int)(i % h), col = (int)(i / h);
-        float r_p = src[3 * i], g_p = src[3 * i + 1], b_p = src[3 * i + 2];
-        float lum_p = denoise_luminance(r_p, g_p, b_p);
-        float nx = normal[3 * i], ny = normal[3 * i + 1], nz = normal[3 * i + 2];
-        float d_p = depth[i];
-        float var_p = P.use_variance ? variance[i] : 0.0f;
-        // weight_color's sigma (:76-88) depends on the centre pixel only
-        float sigma_c = var_p > 0.0f ? P.sigma_color * sqrtf(var_p) + 1.0e-4f : P.sigma_color;
-        float sigma_d = P.sigma_depth * (float)step + 1.0e-4f;
-        float sr = 0.0f, sg = 0.0f, sb = 0.0f, sw = 0.0f;
-        for (int dyi = 0; dyi < 5; ++dyi)
-            for (int dxi = 0; dxi < 5; ++dxi) {
-                int qr = row + (dyi - 2) * step, qc = col + (dxi - 2) * step;
-                qr = qr < 0 ? 0 : (qr > h - 1 ? h - 1 : qr);
-                qc = qc < 0 ? 0 : (qc > w - 1 ? w - 1 : qc);
-                long q = (long)qc * h + qr;
-                float r_q = src[3 * q], g_q = src[3 * q + 1], b_q = src[3 * q + 2];
-                float lum_q = denoise_luminance(r_q, g_q, b_q);
-                float w_spatial = K1D[dxi] * K1D[dyi];
-                float w_color = expf(-fabsf(lum_p - lum_q) / sigma_c);
-                float dotv = nx * normal[3 * q] + ny * normal[3 * q + 1] + nz * normal[3 * q + 2];
-                float w_norm = powf(maxf(0.0f, dotv), P.sigma_normal);
-                float w_depth = expf(-fabsf(d_p - depth[q]) / sigma_d);
-                float weight = w_spatial * w_color * w_norm * w_depth;
-                sr += r_q * weight;
-                sg += g_q * weight;
-                sb += b_q * weight;
-                sw += weight;
-            }
-        if (sw > 1.0e-6f) {   // false for NaN (centre depth +Inf against +Inf neighbours): the pixel is kept
-            float inv = 1.0f / sw;
-            dst[3 * i] = sr * inv, dst[3 * i + 1] = sg * inv, dst[3 * i + 2] = sb * inv;
-        } else
-            dst[3 * i] = r_p, dst[3 * i + 1] = g_p, dst[3 * i + 2] = b_p;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// PRESENT (hk_film_update_aux / hk_film_present): finalize -> variance -> a-trous passes -> postprocess on buffers the film owns, in
-// PACKED records of one float4 per pixel, Julia [h,w] order (i = col * h + row): frame = (r, g, b, lum) with lum = denoise_luminance
-// computed once where the pixel is written, guides = (nx, ny, nz, depth).  A tap is two 16-byte loads and no luminance.  Every
-// expression is the one of k_finalize / k_aux / k_denoise_* / k_postprocess above, operation for operation and in the same order: the
-// chain returns, bit for bit, what hk_film_read_rgb -> hk_denoise -> hk_postprocess return (tests/test_film_present.py).
-// ---------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(HK_TRACE_BLOCK) k_aux_packed(DScene sc, DCamera cam, int h, int w, float miss_depth, float* __restrict__ albedo, float4* __restrict__ guides) {
-    __shared__ int lds_stack[(HK_TRACE_BLOCK / 64) * HK_LDS_STACK * 64];
-    int* stack = lds_stack + (threadIdx.x >> 6) * (HK_LDS_STACK * 64);
-    const int lane = lane_id();
-    unsigned a = 0, b = 0;
-    const long n = (long)h * w;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        int row = (int)(i % h) + 1, col = (int)(i / h) + 1;
-        v2 pixel = mk2(((float)col - 1.0f) + 0.5f, ((float)row - 1.0f) + 0.5f);
-        v3 ro, rd;
-        float time;
-        generate_ray(cam, pixel, mk2(0.5f, 0.5f), 0.0f, ro, rd, time);
-        bool opaque;
-        HitRec hr = traverse<0, false>(sc, ro, rd, INF_F, stack, lane, a, b, opaque);
-        float alb = 0.0f, d = miss_depth;
-        v3 nn = mk3(0, 0, 0);
-        if (hr.prim >= 0) {
-            nn = geometric_normal(sc, hr.prim);
-            v3 hp = ro + rd * hr.t;
-            v3 dd = hp - ro;
-            d = sqrtf(dd.x * dd.x + dd.y * dd.y + dd.z * dd.z);
-            alb = 0.8f;
-        }
-        albedo[3 * i] = albedo[3 * i + 1] = albedo[3 * i + 2] = alb;
-        guides[i] = make_float4(nn.x, nn.y, nn.z, d);
-    }
-}
-// k_finalize into the packed frame
-template <typename ACC>
-__global__ void __launch_bounds__(256) k_present_prepare(const ACC* __restrict__ accum, float4* __restrict__ frame, int width, int height) {
-    size_t N = (size_t)width * height;
-    for (size_t p = blockIdx.x * (size_t)blockDim.x + threadIdx.x; p < N; p += (size_t)gridDim.x * blockDim.x) {
-        int px = (int)(p % width), py = (int)(p / width);
-        ACC w = accum[3 * N + p];
-        float r = 0.0f, g = 0.0f, b = 0.0f;
-        if (w > (ACC)0) {
-            ACC inv = (ACC)1 / w;
-            r = (float)(accum[3 * p] * inv);
-            g = (float)(accum[3 * p + 1] * inv);
-            b = (float)(accum[3 * p + 2] * inv);
-        }
-        frame[(size_t)py + (size_t)height * px] = make_float4(r, g, b, denoise_luminance(r, g, b));
-    }
-}
-// k_denoise_variance over the stored luminances
-__global__ void __launch_bounds__(256) k_present_variance(const float4* __restrict__ frame, float* __restrict__ variance, int h, int w) {
-    const long n = (long)h * w;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        int row = (int)(i % h), col = (int)(i / h);
-        float sum = 0.0f, sum_sq = 0.0f;
-        int count = 0;
-        for (int dy = -1; dy <= 1; ++dy)
-            for (int dx = -1; dx <= 1; ++dx) {
-                int qr = row + dy, qc = col + dx;
-                if (qr >= 0 && qr < h && qc >= 0 && qc < w) {
-                    float lum = frame[(long)qc * h + qr].w;
-                    sum += lum;
-                    sum_sq += lum * lum;
-                    ++count;
-                }
-            }
-        float mean = sum / (float)count, mean_sq = sum_sq / (float)count;
-        variance[i] = maxf(0.0f, mean_sq - mean * mean);
-    }
-}
-// k_postprocess's arithmetic on one pixel (r, g, b: the linear frame); the depths of the escaped mask are the guides' fourth component
-HKD void present_postprocess(const hk_postprocess_params& P, float& r, float& g, float& b, long i, const float4* __restrict__ guides, int h, int w) {
-    r = r * P.exposure, g = g * P.exposure, b = b * P.exposure;
-    if (P.apply_wb) {
-        float ro = P.wb[0] * r + P.wb[1] * g + P.wb[2] * b, go = P.wb[3] * r + P.wb[4] * g + P.wb[5] * b, bo = P.wb[6] * r + P.wb[7] * g + P.wb[8] * b;
-        r = maxf(0.0f, ro), g = maxf(0.0f, go), b = maxf(0.0f, bo);
-    }
-    r = r * P.imaging_ratio, g = g * P.imaging_ratio, b = b * P.imaging_ratio;
-    switch (P.tonemap) {
-        case HK_TONEMAP_REINHARD: {
-            float lum = 0.2126f * r + 0.7152f * g + 0.0722f * b;
-            float sc = lum > 0.0f ? 1.0f / (1.0f + lum) : 1.0f;
-            r = clampf(r * sc, 0.0f, 1.0f), g = clampf(g * sc, 0.0f, 1.0f), b = clampf(b * sc, 0.0f, 1.0f);
-        } break;
-        case HK_TONEMAP_REINHARD_EXT: {
-            float lum = 0.2126f * r + 0.7152f * g + 0.0722f * b;
-            float lw2 = P.white_point * P.white_point;
-            float sc = lum > 0.0f ? (1.0f + lum / lw2) / (1.0f + lum) : 1.0f;
-            r = clampf(r * sc, 0.0f, 1.0f), g = clampf(g * sc, 0.0f, 1.0f), b = clampf(b * sc, 0.0f, 1.0f);
-        } break;
-        case HK_TONEMAP_ACES: {
-            const float a = 2.51f, bc = 0.03f, c = 2.43f, d = 0.59f, e = 0.14f;
-            r = clampf((r * (a * r + bc)) / (r * (c * r + d) + e), 0.0f, 1.0f);
-            g = clampf((g * (a * g + bc)) / (g * (c * g + d) + e), 0.0f, 1.0f);
-            b = clampf((b * (a * b + bc)) / (b * (c * b + d) + e), 0.0f, 1.0f);
-        } break;
-        case HK_TONEMAP_UNCHARTED2: {
-            float ws = 1.0f / pp_unch2(11.2f);
-            r = clampf(pp_unch2(r * 2.0f) * ws, 0.0f, 1.0f), g = clampf(pp_unch2(g * 2.0f) * ws, 0.0f, 1.0f), b = clampf(pp_unch2(b * 2.0f) * ws, 0.0f, 1.0f);
-        } break;
-        case HK_TONEMAP_FILMIC: r = pp_filmic(r), g = pp_filmic(g), b = pp_filmic(b); break;
-        default: r = clampf(r, 0.0f, 1.0f), g = clampf(g, 0.0f, 1.0f), b = clampf(b, 0.0f, 1.0f); break;
-    }
-    if (P.apply_gamma) r = powf(r, P.inv_gamma), g = powf(g, P.inv_gamma), b = powf(b, P.inv_gamma);
-    if (P.mask_escaped && guides) {
-        int row = (int)(i % h) + 1, col = (int)(i / h) + 1;
-        int d_row = h - row + 1;  // Y flip
-        int escaped = 0, total = 0;
-        for (int dr = -1; dr <= 1; ++dr)
-            for (int dc = -1; dc <= 1; ++dc) {
-                int nr = d_row + dr, nc = col + dc;
-                if (nr >= 1 && nr <= h && nc >= 1 && nc <= w) {
-                    escaped += isinf(guides[(long)(nc - 1) * h + nr - 1].w) ? 1 : 0;
-                    total += 1;
-                }
-            }
-        float alpha = (float)escaped / (float)total;
-        r = r * (1.0f - alpha) + P.bg[0] * alpha, g = g * (1.0f - alpha) + P.bg[1] * alpha, b = b * (1.0f - alpha) + P.bg[2] * alpha;
-    }
-}
-// prepare -> postprocess with no a-trous pass between them (no denoise, or iterations == 0)
-__global__ void __launch_bounds__(256) k_present_post(hk_postprocess_params PP, const float4* __restrict__ frame, const float4* __restrict__ guides, float* __restrict__ out, int h, int w) {
-    const long n = (long)h * w;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        float4 c = frame[i];
-        float r = c.x, g = c.y, b = c.z;
-        present_postprocess(PP, r, g, b, i, guides, h, w);
-        out[3 * i] = r, out[3 * i + 1] = g, out[3 * i + 2] = b;
-    }
-}
-// One pixel of k_denoise_atrous: cp / gp the centre's records, fetch(dyi, dxi, cq, gq) the records of tap (dyi, dxi), clamped to the
-// edge.  FINAL: the last pass applies the postprocess (apply_pp) to its own result and writes the 3-float output frame.
-template <bool FINAL, class Fetch>
-HKD void present_atrous_pixel(const hk_denoise_params& P, const hk_postprocess_params& PP, int apply_pp, int step, float4 cp, float4 gp, float var_p, Fetch fetch, long i,
-                              const float4* __restrict__ guides, float4* __restrict__ dst, float* __restrict__ out, int h, int w) {
-    const float K1D[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
-    float r_p = cp.x, g_p = cp.y, b_p = cp.z;
-    float lum_p = cp.w;
-    float nx = gp.x, ny = gp.y, nz = gp.z;
-    float d_p = gp.w;
-    float sigma_c = var_p > 0.0f ? P.sigma_color * sqrtf(var_p) + 1.0e-4f : P.sigma_color;
-    float sigma_d = P.sigma_depth * (float)step + 1.0e-4f;
-    float sr = 0.0f, sg = 0.0f, sb = 0.0f, sw = 0.0f;
-#pragma unroll
-    for (int dyi = 0; dyi < 5; ++dyi)
-#pragma unroll
-        for (int dxi = 0; dxi < 5; ++dxi) {
-            float4 cq, gq;
-            fetch(dyi, dxi, cq, gq);
-            float r_q = cq.x, g_q = cq.y, b_q = cq.z;
-            float lum_q = cq.w;
-            float w_spatial = K1D[dxi] * K1D[dyi];
-            float w_color = expf(-fabsf(lum_p - lum_q) / sigma_c);
-            float dotv = nx * gq.x + ny * gq.y + nz * gq.z;
-            float w_norm = powf(maxf(0.0f, dotv), P.sigma_normal);
-            float w_depth = expf(-fabsf(d_p - gq.w) / sigma_d);
-            float weight = w_spatial * w_color * w_norm * w_depth;
-            sr += r_q * weight;
-            sg += g_q * weight;
-            sb += b_q * weight;
-            sw += weight;
-        }
-    float r = r_p, g = g_p, b = b_p;
-    if (sw > 1.0e-6f) {   // false for NaN (centre depth +Inf against +Inf neighbours): the pixel is kept
-        float inv = 1.0f / sw;
-        r = sr * inv, g = sg * inv, b = sb * inv;
-    }
-    if (FINAL) {
-        if (apply_pp) present_postprocess(PP, r, g, b, i, guides, h, w);
-        out[3 * i] = r, out[3 * i + 1] = g, out[3 * i + 2] = b;
-    } else
-        dst[i] = make_float4(r, g, b, denoise_luminance(r, g, b));
-}
-// One a-trous pass on the packed arrays, one thread per pixel along the contiguous dimension, the taps from global memory at every step
-// (an LDS tile of 32 x 8 pixels + halo for steps 1 and 2 was built and measured: no gain outside the spread, LAB_NOTEBOOK — not kept).
-template <bool FINAL>
-__global__ void __launch_bounds__(256) k_present_atrous(hk_denoise_params P, hk_postprocess_params PP, int apply_pp, int step, const float4* __restrict__ frame,
-                                                        const float4* __restrict__ guides, const float* __restrict__ variance, float4* __restrict__ dst, float* __restrict__ out, int h, int w) {
-    const long n = (long)h * w;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        int row = (int)(i % h), col = (int)(i / h);
-        auto fetch = [&](int dyi, int dxi, float4& cq, float4& gq) {
-            int qr = row + (dyi - 2) * step, qc = col + (dxi - 2) * step;
-            qr = qr < 0 ? 0 : (qr > h - 1 ? h - 1 : qr);
-            qc = qc < 0 ? 0 : (qc > w - 1 ? w - 1 : qc);
-            long q = (long)qc * h + qr;
-            cq = frame[q];
-            gq = guides[q];
-        };
-        present_atrous_pixel<FINAL>(P, PP, apply_pp, step, frame[i], guides[i], P.use_variance ? variance[i] : 0.0f, fetch, i, guides, dst, out, h, w);
-    }
-}
+#include "hk_display.h"
 
 // ---------------------------------------------------------------------------------------------------
 // SCENE EDITS (hk_scene_set_transform).  k_xform_tris rewrites the geometry of a triangle range from the base copies (the arrays as

@@ -34,21 +34,18 @@ bool launch_small_pass(hipStream_t s, int n_cu, const DPathState& st, const DSce
                        uint32_t kinds_mask, DStats* stats, bool dry, void* accum, int film_mode);
 void launch_segment_lists(hipStream_t s, const DPathState& st, int n, const int* depths, const int* queues);
 void launch_film(hipStream_t s, const DPathState& st, const DFrame& fr, const DTables& T, void* accum, bool f64);
-void launch_finalize(hipStream_t s, const void* accum, bool f64, float* out, int w, int h);
 
 // ---- sampler tables, image passes, scene edits ----
 void launch_sobol_table(hipStream_t s, const DSobol& sob, const DFrame& fr, uint2* table, int rows);
 void launch_sobol_lo_table(hipStream_t s, const DSobol& sob, const DFrame& fr, uint16_t* table, int rows, int base, int stride, int count);
-void launch_aux(hipStream_t s, const DScene& sc, const DCamera& cam, int h, int w, float miss_depth, float* albedo, float* normal, float* depth);
-void launch_postprocess(hipStream_t s, const hk_postprocess_params& P, const float* src, const float* depth, float* dst, int h, int w);
-void launch_denoise_variance(hipStream_t s, const float* src, float* variance, int h, int w);
-void launch_denoise_atrous(hipStream_t s, const hk_denoise_params& P, int step, const float* src, const float* normal, const float* depth, const float* variance, float* dst, int h, int w);
-void launch_aux_packed(hipStream_t s, const DScene& sc, const DCamera& cam, int h, int w, float miss_depth, float* albedo, float4* guides);
-void launch_present_prepare(hipStream_t s, const void* accum, bool f64, float4* frame, int w, int h);
-void launch_present_variance(hipStream_t s, const float4* frame, float* variance, int h, int w);
-void launch_present_post(hipStream_t s, const hk_postprocess_params& PP, const float4* frame, const float4* guides, float* out, int h, int w);
-void launch_present_atrous(hipStream_t s, const hk_denoise_params& P, int step, const float4* frame, const float4* guides, const float* variance, float4* dst, float* out,
-                           const hk_postprocess_params* pp, int h, int w);
+// the display chain (hk_display.h), one launcher per stage over the pixel layout (PlanarPixels / PackedPixels, hk_types.h)
+template <class Layout> void launch_finalize(hipStream_t s, const void* accum, bool f64, Layout out, int w, int h);
+template <class Layout> void launch_aux(hipStream_t s, const DScene& sc, const DCamera& cam, int h, int w, float miss_depth, float* albedo, Layout out);
+template <class Layout> void launch_variance(hipStream_t s, Layout src, float* variance, int h, int w);
+template <class Layout> void launch_postprocess(hipStream_t s, const hk_postprocess_params& P, Layout src, float* out, int h, int w);
+// one a-trous pass src -> dst; packed: out != nullptr makes it the LAST pass, which writes the 3-float frame `out` (pp != nullptr: postprocessed)
+void launch_atrous(hipStream_t s, const hk_denoise_params& P, int step, PlanarPixels src, const float* variance, PlanarPixels dst, int h, int w);
+void launch_atrous(hipStream_t s, const hk_denoise_params& P, int step, PackedPixels src, const float* variance, PackedPixels dst, float* out, const hk_postprocess_params* pp, int h, int w);
 void launch_slot_of_prim(hipStream_t s, const float4* leaf, int n, int* slot_of_prim);
 void launch_xform_tris(hipStream_t s, const DXform& X, int first, int n, const float* bp, const float* bn, const float* bt, const int* slot_of_prim, float* pos, float* nrm, float* tan, float* shade,
                        float4* leaf);

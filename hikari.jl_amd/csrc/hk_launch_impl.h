@@ -363,53 +363,52 @@ void launch_film(hipStream_t s, const DPathState& st, const DFrame& fr, const DT
     else
         hipLaunchKernelGGL(k_film<float>, dim3(g), dim3(256), 0, s, st, fr, T, (float*)accum);
 }
-void launch_finalize(hipStream_t s, const void* accum, bool f64, float* out, int w, int h) {
-    int g = grid_for(w * h, 256, 4096);
-    if (f64)
-        hipLaunchKernelGGL(k_finalize<double>, dim3(g), dim3(256), 0, s, (const double*)accum, out, w, h);
-    else
-        hipLaunchKernelGGL(k_finalize<float>, dim3(g), dim3(256), 0, s, (const float*)accum, out, w, h);
-}
 void launch_sobol_table(hipStream_t s, const DSobol& sob, const DFrame& fr, uint2* table, int rows) {
     hipLaunchKernelGGL(k_sobol_table, dim3(grid_for((long)rows * fr.n_pixels_padded > 0x3fffffff ? 0x3fffffff : rows * fr.n_pixels_padded, 256, 8192)), dim3(256), 0, s, sob, fr, table, rows);
 }
 void launch_sobol_lo_table(hipStream_t s, const DSobol& sob, const DFrame& fr, uint16_t* table, int rows, int base, int stride, int count) {
     hipLaunchKernelGGL(k_sobol_lo_table, dim3(65536), dim3(256), 0, s, sob, fr, table, rows, base, stride, count);
 }
-void launch_postprocess(hipStream_t s, const hk_postprocess_params& P, const float* src, const float* depth, float* dst, int h, int w) {
-    hipLaunchKernelGGL(k_postprocess, dim3(grid_for(h * w, 256, 8192)), dim3(256), 0, s, P, src, depth, dst, h, w);
-}
-void launch_denoise_variance(hipStream_t s, const float* src, float* variance, int h, int w) {
-    hipLaunchKernelGGL(k_denoise_variance, dim3(grid_for(h * w, 256, 8192)), dim3(256), 0, s, src, variance, h, w);
-}
-void launch_denoise_atrous(hipStream_t s, const hk_denoise_params& P, int step, const float* src, const float* normal, const float* depth, const float* variance,
-                           float* dst, int h, int w) {
-    hipLaunchKernelGGL(k_denoise_atrous, dim3(grid_for(h * w, 256, 8192)), dim3(256), 0, s, P, step, src, normal, depth, variance, dst, h, w);
-}
-// ---- present: the display chain on the film's own packed buffers ----
-void launch_aux_packed(hipStream_t s, const DScene& sc, const DCamera& cam, int h, int w, float miss_depth, float* albedo, float4* guides) {
-    hipLaunchKernelGGL(k_aux_packed, dim3(grid_for(h * w, HK_TRACE_BLOCK, 2048)), dim3(HK_TRACE_BLOCK), 0, s, sc, cam, h, w, miss_depth, albedo, guides);
-}
-void launch_present_prepare(hipStream_t s, const void* accum, bool f64, float4* frame, int w, int h) {
+// ---- the display chain (hk_display.h): one launcher per stage, instantiated for both pixel layouts ----
+template <class Layout>
+void launch_finalize(hipStream_t s, const void* accum, bool f64, Layout out, int w, int h) {
     int g = grid_for(w * h, 256, 4096);
     if (f64)
-        hipLaunchKernelGGL(k_present_prepare<double>, dim3(g), dim3(256), 0, s, (const double*)accum, frame, w, h);
+        hipLaunchKernelGGL((k_finalize<double, Layout>), dim3(g), dim3(256), 0, s, (const double*)accum, out, w, h);
     else
-        hipLaunchKernelGGL(k_present_prepare<float>, dim3(g), dim3(256), 0, s, (const float*)accum, frame, w, h);
+        hipLaunchKernelGGL((k_finalize<float, Layout>), dim3(g), dim3(256), 0, s, (const float*)accum, out, w, h);
 }
-void launch_present_variance(hipStream_t s, const float4* frame, float* variance, int h, int w) {
-    hipLaunchKernelGGL(k_present_variance, dim3(grid_for(h * w, 256, 8192)), dim3(256), 0, s, frame, variance, h, w);
+template <class Layout>
+void launch_aux(hipStream_t s, const DScene& sc, const DCamera& cam, int h, int w, float miss_depth, float* albedo, Layout out) {
+    hipLaunchKernelGGL(k_aux<Layout>, dim3(grid_for(h * w, HK_TRACE_BLOCK, 2048)), dim3(HK_TRACE_BLOCK), 0, s, sc, cam, h, w, miss_depth, albedo, out);
 }
-void launch_present_post(hipStream_t s, const hk_postprocess_params& PP, const float4* frame, const float4* guides, float* out, int h, int w) {
-    hipLaunchKernelGGL(k_present_post, dim3(grid_for(h * w, 256, 8192)), dim3(256), 0, s, PP, frame, guides, out, h, w);
+template <class Layout>
+void launch_variance(hipStream_t s, Layout src, float* variance, int h, int w) {
+    hipLaunchKernelGGL(k_variance<Layout>, dim3(grid_for(h * w, 256, 8192)), dim3(256), 0, s, src, variance, h, w);
 }
-// one a-trous pass; out != nullptr: the LAST pass (pp != nullptr: with the postprocess), else frame -> dst
-void launch_present_atrous(hipStream_t s, const hk_denoise_params& P, int step, const float4* frame, const float4* guides, const float* variance, float4* dst, float* out,
-                           const hk_postprocess_params* pp, int h, int w) {
+template <class Layout>
+void launch_postprocess(hipStream_t s, const hk_postprocess_params& P, Layout src, float* out, int h, int w) {
+    hipLaunchKernelGGL(k_postprocess<Layout>, dim3(grid_for(h * w, 256, 8192)), dim3(256), 0, s, P, src, out, h, w);
+}
+// the host files call these two instantiations of each
+template void launch_finalize<PlanarPixels>(hipStream_t, const void*, bool, PlanarPixels, int, int);
+template void launch_aux<PlanarPixels>(hipStream_t, const DScene&, const DCamera&, int, int, float, float*, PlanarPixels);
+template void launch_variance<PlanarPixels>(hipStream_t, PlanarPixels, float*, int, int);
+template void launch_postprocess<PlanarPixels>(hipStream_t, const hk_postprocess_params&, PlanarPixels, float*, int, int);
+template void launch_finalize<PackedPixels>(hipStream_t, const void*, bool, PackedPixels, int, int);
+template void launch_aux<PackedPixels>(hipStream_t, const DScene&, const DCamera&, int, int, float, float*, PackedPixels);
+template void launch_variance<PackedPixels>(hipStream_t, PackedPixels, float*, int, int);
+template void launch_postprocess<PackedPixels>(hipStream_t, const hk_postprocess_params&, PackedPixels, float*, int, int);
+template <class Layout, bool FINAL>
+static void atrous(hipStream_t s, const hk_denoise_params& P, int step, Layout src, const float* variance, Layout dst, float* out, const hk_postprocess_params* pp, int h, int w) {
     const hk_postprocess_params PP = pp ? *pp : hk_postprocess_params{};
-    with_bool(out != nullptr, [&](auto FINAL) {
-        hipLaunchKernelGGL(k_present_atrous<decltype(FINAL)::value>, dim3(grid_for(h * w, 256, 8192)), dim3(256), 0, s, P, PP, pp ? 1 : 0, step, frame, guides, variance, dst, out, h, w);
-    });
+    hipLaunchKernelGGL((k_atrous<Layout, FINAL>), dim3(grid_for(h * w, 256, 8192)), dim3(256), 0, s, P, PP, pp ? 1 : 0, step, src, variance, dst, out, h, w);
+}
+void launch_atrous(hipStream_t s, const hk_denoise_params& P, int step, PlanarPixels src, const float* variance, PlanarPixels dst, int h, int w) {
+    atrous<PlanarPixels, false>(s, P, step, src, variance, dst, nullptr, nullptr, h, w);
+}
+void launch_atrous(hipStream_t s, const hk_denoise_params& P, int step, PackedPixels src, const float* variance, PackedPixels dst, float* out, const hk_postprocess_params* pp, int h, int w) {
+    with_bool(out != nullptr, [&](auto FINAL) { atrous<PackedPixels, decltype(FINAL)::value>(s, P, step, src, variance, dst, out, pp, h, w); });
 }
 void launch_slot_of_prim(hipStream_t s, const float4* leaf, int n, int* slot_of_prim) {
     hipLaunchKernelGGL(k_slot_of_prim, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, leaf, n, slot_of_prim);
@@ -420,9 +419,6 @@ void launch_xform_tris(hipStream_t s, const DXform& X, int first, int n, const f
 }
 void launch_refit_level(hipStream_t s, int begin, int end, DNode* nodes, DQNode* qnodes, const DQGrid& grid, const float4* leaf, const float* pos) {
     hipLaunchKernelGGL(k_refit_level, dim3(grid_for(end - begin, 256, 8192)), dim3(256), 0, s, begin, end, nodes, qnodes, grid, leaf, pos);
-}
-void launch_aux(hipStream_t s, const DScene& sc, const DCamera& cam, int h, int w, float miss_depth, float* albedo, float* normal, float* depth) {
-    hipLaunchKernelGGL(k_aux, dim3(grid_for(h * w, HK_TRACE_BLOCK, 2048)), dim3(HK_TRACE_BLOCK), 0, s, sc, cam, h, w, miss_depth, albedo, normal, depth);
 }
 
 }  // namespace hk

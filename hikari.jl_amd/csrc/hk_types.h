@@ -409,3 +409,30 @@ struct DFrame {            // per-pass constants
     int refill_idle;       // k_track: idle lanes that trigger a refill round (HK_TRACK_REFILL_IDLE)
     int walk_tune;         // k_shadow_walk: tracking batches per round | advance steps per batch << 8 | feed rounds << 16 | idle lanes that trigger a refill << 24 (HK_SHADOW_TRACK_BATCH, HK_TRACK_ADVANCE, HK_SHADOW_FEED_ROUNDS, HK_WALK_REFILL_IDLE)
 };
+
+// ---- the two pixel layouts of the display chain (hk_display.h); all images Julia [h,w] column-major, q = col * h + row ----
+// color(q) -> (r, g, b, lum), guide(q) -> (nx, ny, nz, depth); has_depth / depth_at serve the escaped-ray mask (a frame without guides has none)
+__device__ __forceinline__ float luminance709(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
+struct PlanarPixels {   // host-array entry points: three floats per pixel, the luminance computed at every load
+    float *rgb, *normal, *depth;
+    static constexpr int tap_unroll = 1;   // the 25 taps of an a-trous pass stay loops: unrolled, this layout's pass takes 192 VGPRs (2 waves per SIMD, not 8)
+    __device__ __forceinline__ float4 color(long q) const {
+        const float r = rgb[3 * q], g = rgb[3 * q + 1], b = rgb[3 * q + 2];
+        return make_float4(r, g, b, luminance709(r, g, b));
+    }
+    __device__ __forceinline__ float4 guide(long q) const { return make_float4(normal[3 * q], normal[3 * q + 1], normal[3 * q + 2], depth[q]); }
+    __device__ __forceinline__ bool has_depth() const { return depth != nullptr; }
+    __device__ __forceinline__ float depth_at(long q) const { return depth[q]; }
+    __device__ __forceinline__ void store_color(long q, float r, float g, float b) const { rgb[3 * q] = r, rgb[3 * q + 1] = g, rgb[3 * q + 2] = b; }
+    __device__ __forceinline__ void store_guide(long q, float4 g) const { normal[3 * q] = g.x, normal[3 * q + 1] = g.y, normal[3 * q + 2] = g.z, depth[q] = g.w; }
+};
+struct PackedPixels {   // buffers of the film (hk_film_update_aux, hk_film_present): one float4 per record, the luminance computed once, at the store
+    float4 *frame, *guides;
+    static constexpr int tap_unroll = 5;   // ... are unrolled: 25 x two 16-byte loads in flight
+    __device__ __forceinline__ float4 color(long q) const { return frame[q]; }
+    __device__ __forceinline__ float4 guide(long q) const { return guides[q]; }
+    __device__ __forceinline__ bool has_depth() const { return guides != nullptr; }
+    __device__ __forceinline__ float depth_at(long q) const { return guides[q].w; }
+    __device__ __forceinline__ void store_color(long q, float r, float g, float b) const { frame[q] = make_float4(r, g, b, luminance709(r, g, b)); }
+    __device__ __forceinline__ void store_guide(long q, float4 g) const { guides[q] = g; }
+};

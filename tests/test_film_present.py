@@ -1,9 +1,11 @@
 """hk_film_update_aux / hk_film_read_aux / hk_film_present / hk_film_present_async: the display chain kept on the device.
 
 The yardstick is the host chain of the same library — hk_film_read_rgb -> hk_film_fill_aux -> hk_denoise -> hk_postprocess, pinned
-to the oracle by test_gpu_denoise_matches_oracle, test_postprocess_parity and test_aux_buffers_parity.  The device chain keeps every
-expression of those kernels operation for operation, so the frames are compared as uint32 views: equal, not close (NaN-free and
-NaN-kept pixels both count)."""
+to the oracle by test_gpu_denoise_matches_oracle, test_postprocess_parity and test_aux_buffers_parity.  Both chains instantiate the same
+per-pixel functions (hk_display.h: finalize_pixel, first_hit_guides, variance_pixel, atrous_pixel, postprocess_pixel) over two pixel
+layouts — k_finalize / k_aux / k_variance / k_atrous / k_postprocess<PlanarPixels> for the host chain, <PackedPixels> for the device
+chain — so the frames are compared as uint32 views: equal, not close (NaN-free and NaN-kept pixels both count).  What is left to differ is the
+layouts' loads and stores, the luminance kept in the packed record, and the postprocess fused into the last packed pass."""
 import ctypes as C
 
 import numpy as np

@@ -7,10 +7,10 @@ Prints one JSON line (every figure the median of --reps warm repetitions, spread
   present_device_ms        the same call between two events on the context's stream (kernels + the one copy)
   loop_present_async_ms    ms per call of a loop of one-sample renders with hk_film_present_async one call behind
   loop_read_rgb_async_ms   the same loop with the plain hk_film_read_rgb_async: the difference is what the denoise costs on top
-  step1_old_device_ms      one step-1 pass of k_denoise_atrous: event time of hk_denoise with 1 iteration minus with 0 (no variance;
+  step1_old_device_ms      one step-1 pass of k_atrous<PlanarPixels>: event time of hk_denoise with 1 iteration minus with 0 (no variance;
                            uploads and downloads are the same in both)
-  step1_new_device_ms      one step-1 pass of k_present_atrous plus k_present_prepare: event time of hk_film_present with 1 iteration
-                           (no variance, no postprocess) minus the plain finalize-and-copy — an upper bound for the pass
+  step1_new_device_ms      one step-1 pass of k_atrous<PackedPixels> plus the packed k_finalize: event time of hk_film_present with 1
+                           iteration (no variance, no postprocess) minus the plain finalize-and-copy — an upper bound for the pass
                            Both are differences of event times around whole calls: the quartiles are a quarter of the values.  They
                            say whether a pass got slower, not by how much it got faster; a kernel trace gives the durations.
 Usage: python tools/present_timing.py [--size 800] [--reps 15]
