@@ -140,6 +140,6 @@ EXPORTED_SYMBOLS = [
     "hk_denoise", "hk_test_mix", "hk_test_medium", "hk_test_trace_lean",
     "hk_render_tile", "hk_comm_create", "hk_comm_unique_id", "hk_comm_create_rank", "hk_comm_destroy", "hk_film_reduce",
     "hk_ctx_set_option", "hk_ctx_get_option", "hk_trim_cache", "hk_flush", "hk_film_read_rgb_async", "hk_film_read_wait",
-    "hk_film_pin_host", "hk_film_unpin_host", "hk_scene_set_transform", "hk_scene_update_materials",
+    "hk_film_pin_host", "hk_film_unpin_host", "hk_scene_set_transform", "hk_scene_update_materials", "hk_scene_update_lights", "hk_scene_update_envmap",
     "hk_film_update_aux", "hk_film_read_aux", "hk_film_present", "hk_film_present_async",
 ]

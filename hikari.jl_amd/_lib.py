@@ -44,6 +44,8 @@ def lib():
         "hk_scene_destroy": ([vp], i32),
         "hk_scene_set_transform": ([vp, i32, i32, PF], i32),
         "hk_scene_update_materials": ([vp, i32, i32, C.POINTER(A.hk_material)], i32),
+        "hk_scene_update_lights": ([vp, i32, i32, C.POINTER(A.hk_light)], i32),
+        "hk_scene_update_envmap": ([vp, i32, PF, PF], i32),
         "hk_integrator_create": ([vp, C.POINTER(A.hk_integrator_params), C.POINTER(vp)], i32),
         "hk_integrator_destroy": ([vp], i32),
         "hk_film_create": ([vp, i32, i32, i32, vp, C.POINTER(vp)], i32),

@@ -37,6 +37,28 @@ struct LightBVH {
 };
 // max_poly[i]: max_value of light i's sigmoid polynomial (needed for RGBIlluminantSpectrum luminance)
 void build_light_bvh(const hk_light* lights, int n, LightBVH& out);
+// A light-BVH node as the device walks it: the layout of DLightNode (hk_types.h, which says what the fields are; hk_scene.cpp asserts
+// that the two agree), declared here so that the host-only builder can fill it.
+struct LightNodeRec {
+    float centre[3];
+    float half_diag;
+    float r2;
+    float w[3];
+    float phi, cos_o, cos_e, sin_o;
+    uint32_t bits;
+    uint32_t child1_or_light;
+    uint32_t pad[2];
+};
+// What the device holds of a light set besides the baked records: the nodes in sibling-pair order, the bit trail of every light, the
+// infinite lights (1-based) and the two counts of DScene.  No array is empty (one zeroed entry stands in).  A set of n lights gives at
+// most 2 n node entries, n trails and n infinite lights: the capacities hk_scene_create allocates.
+struct LightTables {
+    std::vector<LightNodeRec> nodes;
+    std::vector<uint32_t> trails;
+    std::vector<int32_t> infinite;
+    int num_bvh = 0, num_infinite = 0;
+};
+void derive_light_tables(const hk_light* lights, int n, LightBVH& bvh, LightTables& out);
 
 // sigmoid-polynomial helpers shared by the host-side bakers (spectral/rgb2spec.jl:17-53, 85-167)
 struct RGB2Spec {

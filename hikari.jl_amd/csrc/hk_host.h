@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <climits>
+#include <cstddef>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -250,8 +251,10 @@ struct hk_scene {
     int n_materials = 0;
     int bvh_nodes = 0, bvh_leaf_tris = 0, bvh_depth = 0;
     hk::LightBVH lbvh;
-    // ---- in-place edits (hk_scene_set_transform, hk_scene_update_materials) ----
+    // ---- in-place edits (hk_scene_set_transform, hk_scene_update_materials, hk_scene_update_lights, hk_scene_update_envmap) ----
     std::vector<hk_material> h_materials;   // the records as created / last updated: what an update is checked against
+    std::vector<hk_light> h_lights;         // likewise; the light BVH is rebuilt from these
+    std::vector<DEnvMap> h_envmaps;         // the device records as uploaded (sizes and table pointers; marg_func_int and rot may be stale)
     int n_textures = 0, n_spectra = 0;
     std::vector<int> level_start;           // breadth-first node levels: level L is [level_start[L], level_start[L + 1])
     DevBuf base_pos, base_nrm, base_tan, slot_of_prim;   // geometry as created and the leaf slot of every triangle (first transform)
@@ -265,7 +268,7 @@ struct hk_scene {
         float m[12];
     };
     std::map<int, Xf> xf;                   // transform of every triangle interval [key, end): the grid of the quantised nodes
-    struct Staging {                        // pinned upload buffers of material records, reused once their copy has run
+    struct Staging {                        // pinned upload buffers of the edits' records and tables, reused once their copies have run
         void* host = nullptr;
         size_t bytes = 0;
         hipEvent_t ev = nullptr;
@@ -285,9 +288,12 @@ struct hk_scene {
         }
     }
 };
-// hk_scene.cpp; hk_scene_update_materials bakes and classifies with the same two
+// hk_scene.cpp; hk_scene_update_materials bakes and classifies with the same two, hk_scene_update_lights bakes with the third
 void bake_material(const hk::RGB2Spec& t, const hk_material& m, DMaterial& o);
 bool material_alpha_tested(const hk_material& m);
+void bake_light(const hk::RGB2Spec& r2s, const hk_light& l, DLight& o);   // o: zeroed
+// entries of the trails / infinite arrays of a scene of n lights (the node array has twice as many: hk::LightTables)
+inline size_t light_table_capacity(int n_lights) { return n_lights > 0 ? (size_t)n_lights : 1; }
 
 struct hk_film {
     hk_ctx* ctx = nullptr;

@@ -4692,6 +4692,52 @@ __global__ void __launch_bounds__(256) k_refit_level(int begin, int end, DNode* 
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// ENVIRONMENT-MAP TABLES (hk_scene_update_envmap with new texels): Distribution2D(to_Y.(data)) on the device (sampler/sampling.jl:179-262,
+// textures/environment_map.jl:24-45), in the header's arithmetic.  The order of the binary32 additions IS the result, so nothing is
+// scanned in parallel: k_envmap_rows gives every row v of the map to one lane, which walks its nu texels left to right — texel (v, u)
+// is data[v + height * u], so the lanes of a wave read adjacent texels; their table stores are nu floats apart (a sky changes rarely,
+// the table is written once) — and k_envmap_marginal is ONE lane adding the nv row integrals.  Division is the correctly rounded one
+// (the library is built without -fno-hip-fp32-correctly-rounded-divide-sqrt) and nothing is contracted.
+// ---------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(64) k_envmap_rows(const float4* __restrict__ data, int nu, int nv, float* __restrict__ cond_func, float* __restrict__ cond_cdf,
+                                                    float* __restrict__ cond_func_int, float* __restrict__ marg_func) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= nv) return;
+    const float fnu = (float)nu;
+    float* func = cond_func + (size_t)nu * v;
+    float* cdf = cond_cdf + (size_t)(nu + 1) * v;
+    float sum = 0.0f;
+    cdf[0] = 0.0f;
+    for (int u = 0; u < nu; ++u) {
+        const float4 t = data[(size_t)v + (size_t)nv * u];
+        const float y = (0.212671f * t.x + 0.715160f * t.y) + 0.072169f * t.z;   // to_Y
+        func[u] = y;
+        sum = sum + y / fnu;
+        cdf[u + 1] = sum;
+    }
+    cond_func_int[v] = sum;
+    marg_func[v] = sum;
+    if (sum == 0.0f)   // isapprox(x, 0f0): exact zero only
+        for (int u = 1; u <= nu; ++u) cdf[u] = (float)u / fnu;
+    else
+        for (int u = 1; u <= nu; ++u) cdf[u] = cdf[u] / sum;
+}
+__global__ void __launch_bounds__(64) k_envmap_marginal(int nv, const float* __restrict__ marg_func, float* __restrict__ marg_cdf, DEnvMap* __restrict__ record) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const float fnv = (float)nv;
+    float sum = 0.0f;
+    marg_cdf[0] = 0.0f;
+    for (int v = 0; v < nv; ++v) {
+        sum = sum + marg_func[v] / fnv;
+        marg_cdf[v + 1] = sum;
+    }
+    record->marg_func_int = sum;   // the record's own copy: the host never reads it back
+    if (sum == 0.0f)
+        for (int v = 1; v <= nv; ++v) marg_cdf[v] = (float)v / fnv;
+    else
+        for (int v = 1; v <= nv; ++v) marg_cdf[v] = marg_cdf[v] / sum;
+}
 
 #include "hk_launch_impl.h"
 #include "hk_test_kernels.h"

@@ -50,6 +50,7 @@ void launch_slot_of_prim(hipStream_t s, const float4* leaf, int n, int* slot_of_
 void launch_xform_tris(hipStream_t s, const DXform& X, int first, int n, const float* bp, const float* bn, const float* bt, const int* slot_of_prim, float* pos, float* nrm, float* tan, float* shade,
                        float4* leaf);
 void launch_refit_level(hipStream_t s, int begin, int end, DNode* nodes, DQNode* qnodes, const DQGrid& grid, const float4* leaf, const float* pos);
+void launch_envmap_tables(hipStream_t s, const DEnvMap& e, DEnvMap* record);
 
 // ---- sub-kernel entry points of the parity tests (hk_test_kernels.h) ----
 void launch_test_trace(hipStream_t s, const DScene& sc, int n, const float* o, const float* d, const float* tmax, float* t, int* prim, float* uv);

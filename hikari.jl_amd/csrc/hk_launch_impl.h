@@ -420,5 +420,11 @@ void launch_xform_tris(hipStream_t s, const DXform& X, int first, int n, const f
 void launch_refit_level(hipStream_t s, int begin, int end, DNode* nodes, DQNode* qnodes, const DQGrid& grid, const float4* leaf, const float* pos) {
     hipLaunchKernelGGL(k_refit_level, dim3(grid_for(end - begin, 256, 8192)), dim3(256), 0, s, begin, end, nodes, qnodes, grid, leaf, pos);
 }
+// the Distribution2D tables of map `e` (a host copy of the record: sizes and table pointers) from its texels; `record` is the device record
+void launch_envmap_tables(hipStream_t s, const DEnvMap& e, DEnvMap* record) {
+    hipLaunchKernelGGL(k_envmap_rows, dim3((e.nv + 63) / 64), dim3(64), 0, s, e.data, e.nu, e.nv, const_cast<float*>(e.cond_func), const_cast<float*>(e.cond_cdf),
+                       const_cast<float*>(e.cond_func_int), const_cast<float*>(e.marg_func));
+    hipLaunchKernelGGL(k_envmap_marginal, dim3(1), dim3(64), 0, s, e.nv, e.marg_func, const_cast<float*>(e.marg_cdf), record);
+}
 
 }  // namespace hk

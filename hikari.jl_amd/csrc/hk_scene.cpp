@@ -1,7 +1,7 @@
 // hk_scene.cpp — scene upload: hk_scene_create checks a description, then runs the builders below in order (surface classes, BVH and
 // its quantised copy, attributes, textures, spectra, materials, lights and the light BVH, environment maps, media, the device record,
-// the tables of the in-place edits).  Each builder takes what it reads and fills what it writes; hk_scene_edit.cpp reuses bake_material
-// and material_alpha_tested.
+// the tables of the in-place edits).  Each builder takes what it reads and fills what it writes; hk_scene_edit.cpp reuses bake_material,
+// material_alpha_tested and bake_light.
 #include "hk_host.h"
 
 // ---- constant-colour baking (host float32 arithmetic identical to the device/run-time path) ----------
@@ -336,6 +336,7 @@ int upload_medium_interfaces(hk_scene* s, const hk_scene_desc* d) {
     return HK_OK;
 }
 
+}  // namespace
 // ---- lights ----
 void bake_light(const hk::RGB2Spec& r2s, const hk_light& l, DLight& o) {   // o: zeroed
     o.kind = l.kind;
@@ -375,55 +376,7 @@ void bake_light(const hk::RGB2Spec& r2s, const hk_light& l, DLight& o) {   // o:
     }
     o.coef = make_float4(cf[0], cf[1], cf[2], cf[3]);
 }
-void light_node_record(const hk::LightBVHNodeH& n, DLightNode& o) {   // o: zeroed
-    // volatile: every intermediate is rounded to binary32 exactly where the device code rounded it
-    volatile float c[3], dg[3], r[3];
-    for (int k = 0; k < 3; ++k) {
-        volatile float sum = n.bmin[k] + n.bmax[k];
-        c[k] = sum * 0.5f;
-        dg[k] = n.bmax[k] - n.bmin[k];
-    }
-    for (int k = 0; k < 3; ++k) r[k] = n.bmax[k] - c[k];
-    auto dot3 = [](volatile float* a) {
-        volatile float xx = a[0] * a[0], yy = a[1] * a[1], zz = a[2] * a[2];
-        volatile float xy = xx + yy;
-        volatile float t = xy + zz;
-        return (float)t;
-    };
-    for (int k = 0; k < 3; ++k) o.centre[k] = c[k];
-    volatile float nd = std::sqrt(dot3(dg));
-    o.half_diag = nd * 0.5f;
-    o.r2 = dot3(r);
-    for (int k = 0; k < 3; ++k) o.w[k] = n.w[k];
-    o.phi = n.phi, o.cos_o = n.cos_o, o.cos_e = n.cos_e;
-    volatile float cc = n.cos_o * n.cos_o;
-    volatile float om = 1.0f - cc;
-    o.sin_o = std::sqrt(om > 0.0f ? (float)om : 0.0f);
-    o.bits = n.bits;
-    o.child1_or_light = n.child1_or_light;
-}
-// SIBLING-PAIR ORDER on the device.  The host tree is in the reference's order (bvh-light-sampler.jl:26-46: child 0 = index + 1,
-// child 1 stored), in which the two children a descent evaluates at every level lie in two unrelated 64-B lines.  The device
-// walks entry 0 = root, entry 1 = unused, then the children of every inner node as ONE 128-B aligned pair (2k, 2k + 1), pairs in
-// breadth-first order (the top of the tree is contiguous); an inner node's `child1_or_light` is the entry of its child 0.  Same
-// nodes, same arithmetic per node, one line per level instead of two; hk_scene_light_bvh_copy still hands out the host order.
-void sibling_pair_order(std::vector<DLightNode>& tmp) {
-    std::vector<DLightNode> pairs(2);
-    std::memset(pairs.data(), 0, 2 * sizeof(DLightNode));
-    pairs[0] = tmp[0];
-    std::vector<std::pair<uint32_t, uint32_t>> todo{{0u, 0u}};   // (host index, device entry) of inner nodes whose children are not placed yet
-    for (size_t q = 0; q < todo.size(); ++q) {
-        const uint32_t hi = todo[q].first, de = todo[q].second;
-        if (tmp[hi].bits & 2u) continue;
-        const uint32_t h0 = hi + 1, h1 = tmp[hi].child1_or_light - 1, base = (uint32_t)pairs.size();
-        pairs.push_back(tmp[h0]);
-        pairs.push_back(tmp[h1]);
-        pairs[de].child1_or_light = base;
-        todo.emplace_back(h0, base);
-        todo.emplace_back(h1, base + 1);
-    }
-    tmp.swap(pairs);
-}
+namespace {
 // The light records, the light BVH and its lists.  has_escape: an ambient or environment light is among them.
 // (The parent of this code also kept a `textured_emitters` flag for DScene::simple_lights; it was set only in the branch of the lights
 // that are NOT DiffuseAreaLights, under the condition that the light is one, i.e. never.  simple_lights is what has always run:
@@ -437,19 +390,24 @@ int upload_lights(hk_scene* s, const hk_scene_desc* d, const hk::RGB2Spec& r2s, 
         if (d->lights[i].kind == HK_LIGHT_AMBIENT || d->lights[i].kind == HK_LIGHT_ENVIRONMENT) has_escape = 1;
     }
     HIP_TRY(s->lights.upload(dl.data(), dl.size() * sizeof(DLight)));
-    hk::build_light_bvh(d->lights, d->n_lights, s->lbvh);
-    static_assert(sizeof(DLightNode) == 64, "light node layout");
-    std::vector<DLightNode> tmp(s->lbvh.nodes.size() ? s->lbvh.nodes.size() : 1);
-    std::memset(tmp.data(), 0, tmp.size() * sizeof(DLightNode));
-    for (size_t i = 0; i < s->lbvh.nodes.size(); ++i) light_node_record(s->lbvh.nodes[i], tmp[i]);
-    if (!s->lbvh.nodes.empty()) sibling_pair_order(tmp);
-    HIP_TRY(s->lnodes.upload(tmp.data(), tmp.size() * sizeof(DLightNode)));
-    std::vector<uint32_t> tr = s->lbvh.bit_trails;
-    if (tr.empty()) tr.resize(1);
-    HIP_TRY(s->trails.upload(tr.data(), tr.size() * 4));
-    std::vector<int32_t> inf = s->lbvh.infinite;
-    if (inf.empty()) inf.resize(1);
-    HIP_TRY(s->infinite.upload(inf.data(), inf.size() * 4));
+    static_assert(sizeof(DLightNode) == 64 && sizeof(hk::LightNodeRec) == sizeof(DLightNode), "light node layout");
+    static_assert(offsetof(hk::LightNodeRec, half_diag) == offsetof(DLightNode, half_diag) && offsetof(hk::LightNodeRec, w) == offsetof(DLightNode, w) &&
+                      offsetof(hk::LightNodeRec, sin_o) == offsetof(DLightNode, sin_o) && offsetof(hk::LightNodeRec, child1_or_light) == offsetof(DLightNode, child1_or_light),
+                  "light node layout");
+    hk::LightTables t;
+    hk::derive_light_tables(d->lights, d->n_lights, s->lbvh, t);
+    // each array at the capacity the light count allows (light_table_capacity), the rest zeroed: hk_scene_update_lights rewrites them in
+    // place when lights enter or leave the tree, and only the counts of DScene change
+    auto put = [](DevBuf& b, const void* src, size_t bytes, size_t cap) -> hipError_t {
+        hipError_t e = b.alloc(cap);
+        if (e == hipSuccess) e = hipMemset(b.p, 0, cap);
+        if (e == hipSuccess) e = hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice);
+        return e;
+    };
+    const size_t cap = light_table_capacity(d->n_lights);
+    HIP_TRY(put(s->lnodes, t.nodes.data(), t.nodes.size() * sizeof(DLightNode), 2 * cap * sizeof(DLightNode)));
+    HIP_TRY(put(s->trails, t.trails.data(), t.trails.size() * 4, cap * 4));
+    HIP_TRY(put(s->infinite, t.infinite.data(), t.infinite.size() * 4, cap * 4));
     return HK_OK;
 }
 
@@ -479,6 +437,7 @@ int upload_envmaps(hk_scene* s, const hk_scene_desc* d) {
         std::memcpy(o.rot, e.rotation, sizeof o.rot);
     }
     HIP_TRY(s->envmaps.upload(de.data(), de.size() * sizeof(DEnvMap)));
+    s->h_envmaps.assign(de.begin(), de.begin() + (d->n_envmaps > 0 ? d->n_envmaps : 0));
     return HK_OK;
 }
 
@@ -734,6 +693,7 @@ void fill_dscene(hk_scene* s, const hk_scene_desc* d, const BvhUpload& bvh, bool
 void note_edit_tables(hk_scene* s, const hk_scene_desc* d, const hk::BVH& bvh, bool have_qnodes) {
     const int T = d->n_triangles;
     s->h_materials.assign(d->materials, d->materials + d->n_materials);
+    s->h_lights.assign(d->lights, d->lights + d->n_lights);
     s->n_textures = d->n_textures;
     s->n_spectra = d->n_spectra;
     if (!bvh.nodes.empty()) {   // breadth-first order: a level is a contiguous range (bvh_build.cpp)

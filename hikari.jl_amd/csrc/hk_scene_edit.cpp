@@ -1,13 +1,24 @@
-// hk_scene_edit.cpp — in-place scene edits: hk_scene_set_transform (device transform + BVH refit) and hk_scene_update_materials.
+// hk_scene_edit.cpp — in-place scene edits: hk_scene_set_transform (device transform + BVH refit), hk_scene_update_materials,
+// hk_scene_update_lights (records + host rebuild of the light BVH) and hk_scene_update_envmap (rotation, texels + device table build).
 #include "hk_host.h"
 
 // ---- in-place scene edits -----------------------------------------------------------------------------------------------------
-// Neither entry point waits for the device: the noted calls are rendered first (against the scene as it was), the lanes are joined, and
+// No entry point waits for the device: the noted calls are rendered first (against the scene as it was), the lanes are joined, and
 // the work is enqueued on the context's stream behind everything already there.  Every argument is checked before anything changes.
 // Caches keyed by the scene that an edit must not invalidate, and why it does not: DScene::all_opaque and the HK_TRI_OPAQUE bits (opacity
 // class of every material and the medium interfaces are unchanged), kinds_mask (kinds unchanged), simple_lights / has_escape_lights
 // (lights and textures unchanged), bvh_depth and n_nodes (topology unchanged), the light BVH (built from the base geometry, Q18),
 // the context's noted call (flushed) and lanes (joined); the integrator's path state is sized from those flags only.
+// hk_scene_update_lights changes the light set, so it re-derives what is derived from it, through hk_scene_create's own code path
+// (hk::derive_light_tables): the host tree hk_scene::lbvh (hk_scene_light_bvh_copy), the node / trail tables and the two counts
+// DScene::num_bvh_lights / num_infinite_lights.  What else reads the light set, and why it needs nothing more: has_escape_lights and
+// simple_lights depend on the lights' KINDS and on the texture count (both fixed: a changed kind is refused, Le.tex must name a texture
+// the scene has), n_lights is fixed; hk::preselect_lights and small_pass_class (k_small_pass's instantiation) compare num_bvh_lights
+// with HK_PRESELECT_MIN, but per render call and from the DScene of that call, which is passed to every kernel by value at launch — a
+// tree that grows past the threshold is preselected from the next call on, as a fresh scene's would be (the path state carries sel_light
+// whenever the scene has no media, whatever the count); k_light_select_pool's LDS copy of the top of the tree is filled per launch from
+// num_bvh_lights.  The infinite list is a function of the kinds alone and stays as uploaded.
+// hk_scene_update_envmap changes texels, tables and rotation of a map of unchanged size: nothing on the host is derived from those.
 namespace {
 // the transform of the header's arithmetic: m as given, its normal matrix in double, identity => copy
 std::string make_xform(const float* m34, DXform& X) {
@@ -143,6 +154,32 @@ extern "C" int32_t hk_scene_set_transform(hk_scene* s, int32_t first_tri, int32_
 }
 
 namespace {
+// a pinned staging buffer whose previous copies have run (at most four; the oldest is waited for only when all four are in flight)
+int acquire_staging(hk_scene* s, size_t bytes, hk_scene::Staging*& st) {
+    st = nullptr;
+    for (auto& b : s->staging)
+        if (b.bytes >= bytes && hipEventQuery(b.ev) == hipSuccess) {
+            st = &b;
+            break;
+        }
+    if (!st) {
+        if (s->staging.size() < 4) {
+            s->staging.emplace_back();
+            st = &s->staging.back();
+            HIP_TRY(hipEventCreateWithFlags(&st->ev, hipEventDisableTiming));
+        } else {
+            st = &s->staging.front();
+            HIP_TRY(hipEventSynchronize(st->ev));
+        }
+        if (st->bytes < bytes) {
+            if (st->host) HIP_TRY(hipHostFree(st->host));
+            st->host = nullptr, st->bytes = 0;
+            HIP_TRY(hipHostMalloc(&st->host, bytes, hipHostMallocDefault));
+            st->bytes = bytes;
+        }
+    }
+    return HK_OK;
+}
 // what an update may change: everything but the kind, a Mix's children, and the opacity class; indices must stay in range
 std::string check_material_update(const hk_scene* s, int idx, const hk_material& old, const hk_material& m) {
     const std::string at = "hk_scene_update_materials: material " + std::to_string(idx) + ": ";
@@ -172,34 +209,88 @@ extern "C" int32_t hk_scene_update_materials(hk_scene* s, int32_t first, int32_t
     HIP_TRY(hipSetDevice(c->device));
     KnobScope knobs(&c->knobs);
     const size_t bytes = (size_t)n * sizeof(DMaterial);
-    // a pinned staging buffer whose previous copy has run (at most four; the oldest is waited for only when all four are in flight)
     hk_scene::Staging* st = nullptr;
-    for (auto& b : s->staging)
-        if (b.bytes >= bytes && hipEventQuery(b.ev) == hipSuccess) {
-            st = &b;
-            break;
-        }
-    if (!st) {
-        if (s->staging.size() < 4) {
-            s->staging.emplace_back();
-            st = &s->staging.back();
-            HIP_TRY(hipEventCreateWithFlags(&st->ev, hipEventDisableTiming));
-        } else {
-            st = &s->staging.front();
-            HIP_TRY(hipEventSynchronize(st->ev));
-        }
-        if (st->bytes < bytes) {
-            if (st->host) HIP_TRY(hipHostFree(st->host));
-            st->host = nullptr, st->bytes = 0;
-            HIP_TRY(hipHostMalloc(&st->host, bytes, hipHostMallocDefault));
-            st->bytes = bytes;
-        }
-    }
+    if (int e = acquire_staging(s, bytes, st)) return e;
     if (int e = join_lanes(c)) return e;   // noted calls render the old materials; the lanes finish before the stream rewrites them
     DMaterial* rec = static_cast<DMaterial*>(st->host);
     for (int j = 0; j < n; ++j) bake_material(c->r2s_host, materials[j], rec[j]);
     HIP_TRY(hipMemcpyAsync(s->materials.as<DMaterial>() + first, rec, bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipEventRecord(st->ev, c->stream));
     for (int j = 0; j < n; ++j) s->h_materials[first + j] = materials[j];
+    return HK_OK;
+}
+
+extern "C" int32_t hk_scene_update_lights(hk_scene* s, int32_t first, int32_t n, const hk_light* lights) {
+    if (!s || !lights) return fail(HK_ERR_INVALID, "hk_scene_update_lights: null argument");
+    const int NL = (int)s->h_lights.size();
+    if (first < 0 || n < 1 || (int64_t)first + n > NL) return fail(HK_ERR_INVALID, "hk_scene_update_lights: light range outside the scene");
+    for (int j = 0; j < n; ++j) {   // what an update may change: everything but the kind; indices must stay in range (hk_scene_create's checks)
+        const hk_light& l = lights[j];
+        const std::string at = "hk_scene_update_lights: light " + std::to_string(first + j) + ": ";
+        if (l.kind != s->h_lights[first + j].kind) return fail(HK_ERR_INVALID, at + "the kind differs from the record it replaces");
+        if (l.kind == HK_LIGHT_ENVIRONMENT && (l.envmap < 0 || l.envmap >= (int)s->h_envmaps.size())) return fail(HK_ERR_INVALID, at + "environment light refers to a missing envmap");
+        if (l.kind == HK_LIGHT_DIFFUSE_AREA && l.Le.tex >= s->n_textures) return fail(HK_ERR_INVALID, at + "area light: Le texture index out of range");
+    }
+    hk_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    KnobScope knobs(&c->knobs);
+    // the tables of the edited light set, by hk_scene_create's code path; the scene is untouched until everything is enqueued
+    std::vector<hk_light> all = s->h_lights;
+    std::copy(lights, lights + n, all.begin() + first);
+    hk::LightBVH lbvh;
+    hk::LightTables t;
+    hk::derive_light_tables(all.data(), NL, lbvh, t);
+    // one staging block: the n baked records, then the node and trail tables (the capacities of hk_scene_create hold them: LightTables)
+    const size_t b_rec = (size_t)n * sizeof(DLight), b_nodes = t.nodes.size() * sizeof(DLightNode), b_trails = t.trails.size() * 4;
+    hk_scene::Staging* st = nullptr;
+    if (int e = acquire_staging(s, b_rec + b_nodes + b_trails, st)) return e;
+    if (int e = join_lanes(c)) return e;   // noted calls render the old lights; the lanes finish before the stream rewrites them
+    char* h = static_cast<char*>(st->host);
+    DLight* rec = reinterpret_cast<DLight*>(h);
+    std::memset(rec, 0, b_rec);
+    for (int j = 0; j < n; ++j) bake_light(c->r2s_host, lights[j], rec[j]);
+    std::memcpy(h + b_rec, t.nodes.data(), b_nodes);
+    std::memcpy(h + b_rec + b_nodes, t.trails.data(), b_trails);
+    HIP_TRY(hipMemcpyAsync(s->lights.as<DLight>() + first, rec, b_rec, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(s->lnodes.p, h + b_rec, b_nodes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(s->trails.p, h + b_rec + b_nodes, b_trails, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipEventRecord(st->ev, c->stream));
+    s->h_lights.swap(all);
+    s->lbvh = std::move(lbvh);
+    s->d.num_bvh_lights = t.num_bvh;
+    s->d.num_infinite_lights = t.num_infinite;
+    return HK_OK;
+}
+
+extern "C" int32_t hk_scene_update_envmap(hk_scene* s, int32_t idx, const float* data, const float* rotation) {
+    if (!s) return fail(HK_ERR_INVALID, "hk_scene_update_envmap: null scene");
+    if (!data && !rotation) return fail(HK_ERR_INVALID, "hk_scene_update_envmap: neither texels nor a rotation given");
+    if (idx < 0 || idx >= (int)s->h_envmaps.size()) return fail(HK_ERR_INVALID, "hk_scene_update_envmap: map index out of range");
+    if (rotation)
+        for (int j = 0; j < 9; ++j)
+            if (!std::isfinite(rotation[j])) return fail(HK_ERR_INVALID, "hk_scene_update_envmap: non-finite rotation entry");
+    DEnvMap& e = s->h_envmaps[idx];
+    if (data && (e.nu != e.width || e.nv != e.height)) return fail(HK_ERR_INVALID, "hk_scene_update_envmap: the map's tables are not of its texels' resolution (nu != width or nv != height)");
+    hk_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    KnobScope knobs(&c->knobs);
+    const size_t b_rot = 9 * sizeof(float), b_data = data ? (size_t)e.width * e.height * 16 : 0;
+    hk_scene::Staging* st = nullptr;
+    if (int err = acquire_staging(s, b_rot + b_data, st)) return err;
+    if (int err = join_lanes(c)) return err;   // noted calls render the old sky; the lanes finish before the stream rewrites it
+    char* h = static_cast<char*>(st->host);
+    DEnvMap* record = s->envmaps.as<DEnvMap>() + idx;
+    if (rotation) {   // the nine floats of the record and nothing else (marg_func_int lives there too, and only the device knows it)
+        std::memcpy(h, rotation, b_rot);
+        HIP_TRY(hipMemcpyAsync(reinterpret_cast<char*>(record) + offsetof(DEnvMap, rot), h, b_rot, hipMemcpyHostToDevice, c->stream));
+        std::memcpy(e.rot, rotation, b_rot);
+    }
+    if (data) {   // the texels into their buffer, the tables from them into theirs (sizes unchanged)
+        std::memcpy(h + b_rot, data, b_data);
+        HIP_TRY(hipMemcpyAsync(const_cast<float4*>(e.data), h + b_rot, b_data, hipMemcpyHostToDevice, c->stream));
+        hk::launch_envmap_tables(c->stream, e, record);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(st->ev, c->stream));
     return HK_OK;
 }

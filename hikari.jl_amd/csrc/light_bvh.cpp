@@ -275,6 +275,73 @@ void build_light_bvh(const hk_light* lights, int n, LightBVH& out) {
     }
 }
 
+namespace {
+void light_node_record(const LightBVHNodeH& n, LightNodeRec& o) {   // o: zeroed
+    // volatile: every intermediate is rounded to binary32 exactly where the device code rounded it
+    volatile float c[3], dg[3], r[3];
+    for (int k = 0; k < 3; ++k) {
+        volatile float sum = n.bmin[k] + n.bmax[k];
+        c[k] = sum * 0.5f;
+        dg[k] = n.bmax[k] - n.bmin[k];
+    }
+    for (int k = 0; k < 3; ++k) r[k] = n.bmax[k] - c[k];
+    auto dot3 = [](volatile float* a) {
+        volatile float xx = a[0] * a[0], yy = a[1] * a[1], zz = a[2] * a[2];
+        volatile float xy = xx + yy;
+        volatile float t = xy + zz;
+        return (float)t;
+    };
+    for (int k = 0; k < 3; ++k) o.centre[k] = c[k];
+    volatile float nd = std::sqrt(dot3(dg));
+    o.half_diag = nd * 0.5f;
+    o.r2 = dot3(r);
+    for (int k = 0; k < 3; ++k) o.w[k] = n.w[k];
+    o.phi = n.phi, o.cos_o = n.cos_o, o.cos_e = n.cos_e;
+    volatile float cc = n.cos_o * n.cos_o;
+    volatile float om = 1.0f - cc;
+    o.sin_o = std::sqrt(om > 0.0f ? (float)om : 0.0f);
+    o.bits = n.bits;
+    o.child1_or_light = n.child1_or_light;
+}
+// SIBLING-PAIR ORDER on the device.  The host tree is in the reference's order (bvh-light-sampler.jl:26-46: child 0 = index + 1,
+// child 1 stored), in which the two children a descent evaluates at every level lie in two unrelated 64-B lines.  The device
+// walks entry 0 = root, entry 1 = unused, then the children of every inner node as ONE 128-B aligned pair (2k, 2k + 1), pairs in
+// breadth-first order (the top of the tree is contiguous); an inner node's `child1_or_light` is the entry of its child 0.  Same
+// nodes, same arithmetic per node, one line per level instead of two; hk_scene_light_bvh_copy still hands out the host order.
+void sibling_pair_order(std::vector<LightNodeRec>& tmp) {
+    std::vector<LightNodeRec> pairs(2);
+    std::memset(pairs.data(), 0, 2 * sizeof(LightNodeRec));
+    pairs[0] = tmp[0];
+    std::vector<std::pair<uint32_t, uint32_t>> todo{{0u, 0u}};   // (host index, device entry) of inner nodes whose children are not placed yet
+    for (size_t q = 0; q < todo.size(); ++q) {
+        const uint32_t hi = todo[q].first, de = todo[q].second;
+        if (tmp[hi].bits & 2u) continue;
+        const uint32_t h0 = hi + 1, h1 = tmp[hi].child1_or_light - 1, base = (uint32_t)pairs.size();
+        pairs.push_back(tmp[h0]);
+        pairs.push_back(tmp[h1]);
+        pairs[de].child1_or_light = base;
+        todo.emplace_back(h0, base);
+        todo.emplace_back(h1, base + 1);
+    }
+    tmp.swap(pairs);
+}
+}  // namespace
+
+// The device tables of a light set — the ONE path from hk_light records to what the kernels walk: hk_scene_create and
+// hk_scene_update_lights both call it on the scene's whole light array, so an edited scene holds what a fresh one would.
+void derive_light_tables(const hk_light* lights, int n, LightBVH& bvh, LightTables& out) {
+    build_light_bvh(lights, n, bvh);
+    out.nodes.assign(bvh.nodes.size() ? bvh.nodes.size() : 1, LightNodeRec{});
+    for (size_t i = 0; i < bvh.nodes.size(); ++i) light_node_record(bvh.nodes[i], out.nodes[i]);
+    if (!bvh.nodes.empty()) sibling_pair_order(out.nodes);
+    out.trails = bvh.bit_trails;
+    if (out.trails.empty()) out.trails.resize(1);
+    out.infinite = bvh.infinite;
+    if (out.infinite.empty()) out.infinite.resize(1);
+    out.num_bvh = bvh.num_bvh;
+    out.num_infinite = (int)bvh.infinite.size();
+}
+
 // rgb_to_spectrum (spectral/rgb2spec.jl:85-167): host-side bake of constant colours
 void rgb_to_coeffs(const RGB2Spec& t, float r, float g, float b, float out[3]) {
     r = cl(r, 0.0f, 1.0f);

@@ -82,6 +82,31 @@ class EnvironmentMap:
         self.distribution = Distribution2D(lum.astype(f32))
         self._jl = np.ascontiguousarray(np.transpose(self.data, (1, 0, 2)))   # [x][y][4] == Julia [h, w] column-major
 
+    _TABLES = ("conditional_func", "conditional_cdf", "conditional_func_int", "marginal_func", "marginal_cdf")
+
+    def update(self, data=None, rotation=None):
+        """New texels of the same size and / or a new rotation, IN PLACE: the arrays a record() already handed out keep their
+        addresses, so a kept hk_envmap stays valid (its rotation and marginal_func_int are values: Scene.update_envmap rewrites
+        them).  The tables are rebuilt here for the kept description; hk_scene_update_envmap builds the device's own on the device."""
+        if data is None and rotation is None:
+            raise ValueError("update: neither data nor rotation given")
+        rot = None
+        if rotation is not None:
+            rot = np.asarray(rotation, dtype=f32).reshape(3, 3)
+            if not np.isfinite(rot).all():
+                raise ValueError("update: non-finite rotation entry")
+        if data is not None:
+            new = EnvironmentMap(data)
+            if (new.height, new.width) != (self.height, self.width):
+                raise ValueError("update: the map is %dx%d, the new texels are %dx%d (the size cannot change)" % (self.width, self.height, new.width, new.height))
+            self.data[...] = new.data
+            self._jl[...] = new._jl
+            for name in self._TABLES:
+                getattr(self.distribution, name)[...] = getattr(new.distribution, name)
+            self.distribution.marginal_func_int = new.distribution.marginal_func_int
+        if rot is not None:
+            self.rotation = rot.copy()
+
     def record(self):
         r = A.hk_envmap()
         D = self.distribution

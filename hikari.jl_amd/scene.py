@@ -47,6 +47,29 @@ def _affine_3x4(m4x4):
     return m34
 
 
+def _transform_points(m34, p):
+    """hk_scene_set_transform's point formula in binary32: p'[k] = ((m[k][0]*x + m[k][1]*y) + m[k][2]*z) + m[k][3]; [I | 0] copies."""
+    m, p = np.asarray(m34, dtype=f32), np.asarray(p, dtype=f32)
+    if (m == np.eye(3, 4, dtype=f32)).all():
+        return p.copy()
+    x, y, z = p[..., 0], p[..., 1], p[..., 2]
+    out = np.empty_like(p)
+    for k in range(3):
+        out[..., k] = ((m[k, 0] * x + m[k, 1] * y) + m[k, 2] * z) + m[k, 3]
+    return out
+
+
+def _face_light_geometry(vs):
+    """(normal, area) of a face's DiffuseAreaLight (scene-mesh.jl:98-131): edge cross product, its length `twice`, normal = cp / twice,
+    area = twice / 2; None under the 1e-10 cut-off (no light is registered for such a face)."""
+    e1, e2 = (vs[1] - vs[0]).astype(f32), (vs[2] - vs[0]).astype(f32)
+    cp = np.array([e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]], dtype=f32)
+    twice = np.sqrt(f32(f32(cp[0] * cp[0]) + f32(cp[1] * cp[1])) + f32(cp[2] * cp[2]), dtype=f32)
+    if twice < 1e-10:
+        return None
+    return (cp / twice).astype(f32), f32(0.5) * twice
+
+
 def _luminance(c):
     return float(f32(0.212671) * f32(c[0]) + f32(0.715160) * f32(c[1]) + f32(0.072169) * f32(c[2]))
 
@@ -140,18 +163,119 @@ class Scene:
             self._transforms[(first, inst.n_tris)] = m34
         return inst
 
-    def set_transform(self, instance, m4x4):
+    def set_transform(self, instance, m4x4, move_lights=False):
         """update_transform!: the instance's triangles become m4x4 applied to the mesh as pushed, in every device scene already
-        created from this Scene and in those created later."""
+        created from this Scene and in those created later.
+
+        move_lights=False (the default, the reference's behaviour, Q18): the area lights of an emissive instance stay where the mesh
+        was pushed.  move_lights=True: they follow — every face's light is recomputed here from the moved vertices (the header's
+        point formula, then _face_light_geometry as at push time) and sent with hk_scene_update_lights, one call per contiguous run
+        of flat light indices; the light BVH is rebuilt.  A face whose moved edge cross product falls under the 1e-10 cut-off (a
+        push would not have registered it) keeps its record with area = 0: zero power, so it leaves the tree, and comes back with
+        the next transform that gives it an area."""
         if not isinstance(instance, SceneInstance):
             raise TypeError("set_transform takes the SceneInstance push_instance returned")
         m34 = _affine_3x4(m4x4)
         if instance.n_tris < 1 or instance.first_tri < 0 or instance.first_tri + instance.n_tris > self.n_triangles():
             raise ValueError("instance %r is not a triangle range of this scene" % (instance,))
+        moved = self._moved_area_lights(instance, m34) if move_lights else []
         self._transforms[(instance.first_tri, instance.n_tris)] = m34
         from . import _lib
         for h in (getattr(self, "_device", None) or {}).values():
             _lib.check(_lib.lib().hk_scene_set_transform(h, instance.first_tri, instance.n_tris, m34.ctypes.data_as(A.PF)), "hk_scene_set_transform")
+        if moved:
+            self._replace_lights(moved)
+
+    def _moved_area_lights(self, instance, m34):
+        """[(index into self.lights, DiffuseAreaLight)] of the instance's faces that carry a light, from the mesh as pushed moved by m34."""
+        first = 0
+        for mesh, metas in self._meshes:
+            if first == instance.first_tri and mesh.n_faces == instance.n_tris:
+                break
+            first += mesh.n_faces
+        else:
+            raise ValueError("instance %r is not a mesh of this scene" % (instance,))
+        faces = np.nonzero(metas[:, 2])[0]
+        P = _transform_points(m34, mesh.positions[faces])
+        out = []
+        for vs, idx1 in zip(P, metas[faces, 2]):
+            old = self.lights[int(idx1) - 1]
+            geo = _face_light_geometry(vs)
+            normal, area = geo if geo is not None else (np.asarray(old.normal, dtype=f32), 0.0)
+            out.append((int(idx1) - 1, L.DiffuseAreaLight(vs.copy(), normal, float(area), np.array(old.uv, dtype=f32), old.Le, old.scale, old.two_sided)))
+        return out
+
+    # ---- lights and environment maps in place (hk_scene_update_lights, hk_scene_update_envmap) --------------------------------
+    def _flat_index(self, index):
+        light = self.lights[index]
+        for i, l in enumerate(self.flat_lights()):
+            if l is light:
+                return i
+        raise ValueError("light %d is not in the flat order" % index)
+
+    def _replace_lights(self, pairs):
+        """pairs: [(index into self.lights, new light of the same class)].  Rewrites self.lights, the kept description and every
+        device scene — contiguous runs of FLAT indices (flat_lights() order, what hk_scene_desc::lights holds) in one call each."""
+        for index, light in pairs:
+            if not 0 <= index < len(self.lights):
+                raise IndexError("light index %d out of range" % index)
+            if type(light) is not type(self.lights[index]):
+                raise TypeError("update_light: %s cannot replace %s (the class must match)" % (type(light).__name__, type(self.lights[index]).__name__))
+        flat = [self._flat_index(index) for index, _ in pairs]
+        recs = None
+        if self._desc is not None:      # (before the first sync there is no description: the next one flattens the new lights)
+            n_tex, n_env = len(self.textures), len(self._envmaps)
+            try:
+                recs = [self._light_record(light, None) for _, light in pairs]
+                added = len(self.textures) != n_tex or len(self._envmaps) != n_env
+            finally:
+                del self.textures[n_tex:], self._envmaps[n_env:]
+            if added:
+                raise ValueError("update_light: the new light references a texture or an environment map that is not in the scene")
+        for index, light in pairs:
+            self.lights[index] = light
+        if recs is None:
+            return
+        order = sorted(range(len(flat)), key=lambda k: flat[k])
+        from . import _lib
+        k = 0
+        while k < len(order):
+            e = k + 1
+            while e < len(order) and flat[order[e]] == flat[order[e - 1]] + 1:
+                e += 1
+            run = (A.hk_light * (e - k))(*[recs[order[j]] for j in range(k, e)])
+            for j in range(k, e):
+                self._desc.lights[flat[order[j]]] = recs[order[j]]
+            for h in (getattr(self, "_device", None) or {}).values():
+                _lib.check(_lib.lib().hk_scene_update_lights(h, flat[order[k]], e - k, run), "hk_scene_update_lights")
+            k = e
+
+    def update_light(self, index, light):
+        """The light self.lights[index] (0-based position in push order: push_light's return value minus one) is replaced by
+        `light`, an object of the same class: dim a lamp, move a point light, turn the sun, re-colour an emitter (a
+        DiffuseAreaLight: its Le, scale, two_sided, geometry).  The description holds the lights in flat_lights() order; the index
+        is mapped through it."""
+        self._replace_lights([(index, light)])
+
+    def update_envmap(self, env_map, data=None, rotation=None):
+        """New texels (same size, [height, width, 3 or 4]) and / or a new 3x3 rotation for an EnvironmentMap of this scene, in the
+        kept description and in every device scene (which builds the sampling tables from the texels itself)."""
+        env_map.update(data=data, rotation=rotation)        # refuses what the library would refuse (ValueError)
+        if self._desc is None:
+            return
+        for idx, e in enumerate(self._envmaps):
+            if e is env_map:
+                break
+        else:
+            raise ValueError("update_envmap: the map belongs to no EnvironmentLight of this scene")
+        rec = self._desc.envmaps[idx]
+        rec.rotation[:] = [float(x) for x in env_map.rotation.reshape(-1)]
+        rec.marginal_func_int = float(env_map.distribution.marginal_func_int)
+        rot = np.ascontiguousarray(env_map.rotation, dtype=f32) if rotation is not None else None
+        from . import _lib
+        for h in (getattr(self, "_device", None) or {}).values():
+            _lib.check(_lib.lib().hk_scene_update_envmap(h, idx, env_map._jl.ctypes.data_as(A.PF) if data is not None else None,
+                                                        rot.ctypes.data_as(A.PF) if rot is not None else None), "hk_scene_update_envmap")
 
     def _apply_transforms(self, handle):
         from . import _lib
@@ -189,6 +313,7 @@ class Scene:
 
     def _plan_material_update(self, flat, new, plan):
         old = self.materials[flat]
+        # (Emissive stays refused here: an emitter's colour is a property of its area lights — update_light changes it)
         if isinstance(new, (M.MediumInterface, M.Emissive)) or type(new) is not type(old):
             raise TypeError("update_material: %s cannot replace %s (the type must match; emission is not editable)" % (type(new).__name__, type(old).__name__))
         if isinstance(new, M.MixMaterial):
@@ -226,13 +351,10 @@ class Scene:
                 Le = M.RGBSpectrum(*[float(x) for x in np.atleast_1d(texel)[:4]]) if np.ndim(texel) else M.RGBSpectrum(float(texel))
             if _luminance(Le.c) < 1e-4:
                 continue
-            e1, e2 = (vs[1] - vs[0]).astype(f32), (vs[2] - vs[0]).astype(f32)
-            cp = np.array([e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]], dtype=f32)
-            twice = np.sqrt(f32(f32(cp[0] * cp[0]) + f32(cp[1] * cp[1])) + f32(cp[2] * cp[2]), dtype=f32)
-            if twice < 1e-10:
+            geo = _face_light_geometry(vs)
+            if geo is None:
                 continue
-            normal = (cp / twice).astype(f32)
-            area = f32(0.5) * twice
+            normal, area = geo
             self.push_light(L.DiffuseAreaLight(vs.copy(), normal, float(area), uv.copy(), Le, em.scale, em.two_sided))
             metas[i, 2] = len(self.lights)  # flat index = length(scene.lights) at push time
 

@@ -347,7 +347,7 @@ int32_t hk_scene_destroy(hk_scene* scene);
 
 /* ---------------------------------------------------------------------------------------------
  * Editing a scene in place (update_transform!, src/surface_interaction.jl:413-423; update_material!, src/scene.jl:104-112).
- * Both calls first render the noted calls (see hk_render: they were made against the scene as it was), then enqueue their work on
+ * Every call first renders the noted calls (see hk_render: they were made against the scene as it was), then enqueue their work on
  * ctx's stream behind everything already enqueued, and return without waiting for the device.  Films are not cleared.  A refused
  * call (HK_ERR_INVALID, hk_last_error says why) leaves the scene untouched.
  *
@@ -367,9 +367,32 @@ int32_t hk_scene_destroy(hk_scene* scene);
  * hk_scene_update_materials: material records [first, first + n) of hk_scene_desc::materials are replaced by materials[0 .. n-1]
  * (upload through pinned memory owned by the scene).  Refused: a null pointer, n < 1 or a range outside the scene, and a record that
  * changes its kind, a Mix's children (i[0], i[1], mix_key), its opacity class (Matte with an alpha texture or alpha < 1) or names a
- * texture / spectrum index that is out of range. */
+ * texture / spectrum index that is out of range.
+ *
+ * hk_scene_update_lights: light records [first, first + n) of hk_scene_desc::lights are replaced by lights[0 .. n-1].  Everything but
+ * `kind` may change (spectrum, scale, position, direction, the spot matrices and cosines; v, normal, area, uv, Le, two_sided of an area
+ * light).  The light BVH is REBUILT on the host from the scene's whole light array, by the builder hk_scene_create uses, and uploaded
+ * with the baked records: the pmf of the light sampler depends on the tree's shape, and the scene after the call is, bit for bit, the
+ * scene hk_scene_create builds from the edited description.  A light whose power becomes 0 leaves the tree, one whose power becomes
+ * positive enters it.  The triangles of an area light are not moved by this call (nor is a light moved by hk_scene_set_transform).
+ * Refused: a null pointer, n < 1 or a range outside the scene, a record whose kind differs from the one it replaces, an environment
+ * light whose `envmap` or an area light whose `Le.tex` is out of range.
+ *
+ * hk_scene_update_envmap: environment map `idx` of hk_scene_desc::envmaps gets new texels (`data`: width x height texels in the layout
+ * of hk_envmap::data, the sizes unchanged), a new `rotation` (3x3 row-major), or both; either pointer may be NULL, not both.  A rotation
+ * alone rewrites the nine floats of the device record.  With texels the Distribution2D tables are rebuilt ON THE DEVICE from them
+ * (sampler/sampling.jl:179-262 over to_Y of the texels, textures/environment_map.jl:24-45), binary32 without contraction, division
+ * correctly rounded, every sum sequential in index order:
+ *   func[v][u]    = (0.212671f*r + 0.715160f*g) + 0.072169f*b                    of texel (v, u)
+ *   row v         c[0] = 0, c[u+1] = c[u] + func[v][u] / (float)nu;  func_int[v] = c[nu];
+ *                 cdf[v][u] = func_int[v] == 0 ? (float)u / (float)nu : c[u] / func_int[v]          (u = 1 .. nu; cdf[v][0] = 0)
+ *   marginal      the same over func_int[0 .. nv-1] with nv in place of nu; its integral is marginal_func_int
+ * Refused: a null scene, both pointers NULL, idx out of range, a non-finite rotation entry, texels for a map whose tables are not of
+ * the texels' resolution (nu != width or nv != height). */
 int32_t hk_scene_set_transform(hk_scene* scene, int32_t first_tri, int32_t n_tris, const float* m34);
 int32_t hk_scene_update_materials(hk_scene* scene, int32_t first, int32_t n, const hk_material* materials);
+int32_t hk_scene_update_lights(hk_scene* scene, int32_t first, int32_t n, const hk_light* lights);
+int32_t hk_scene_update_envmap(hk_scene* scene, int32_t idx, const float* data, const float* rotation);
 
 int32_t hk_integrator_create(hk_ctx* ctx, const hk_integrator_params* params, hk_integrator** out);
 int32_t hk_integrator_destroy(hk_integrator* integ);
@@ -394,7 +417,7 @@ int32_t hk_film_clear(hk_film* film); /* clear!(vp), volpath.jl:108-113 */
  *     following on) are rendered as ONE pass — bit-identical film, a seventh of the time — when the note reaches HK_BATCH_PATHS_M
  *     (64 M paths), when a call comes that does not continue it, or when anything looks: hk_flush, hk_sync, every hk_film_* / hk_stats_* /
  *     hk_*_destroy / hk_ctx_set_option /
- *     hk_scene_set_transform / hk_scene_update_materials entry point.  hk_flush enqueues the noted calls without waiting for them.
+ *     hk_scene_set_transform / hk_scene_update_materials / hk_scene_update_lights / hk_scene_update_envmap entry point.  hk_flush enqueues the noted calls without waiting for them.
  *     HK_BATCH_PATHS_M=0 (hk_ctx_set_option) turns the noting off.
  * Argument errors are reported by the call itself; a device error of a deferred pass by the call that flushes it — also by the
  * destroy entry points, which still destroy their object. */

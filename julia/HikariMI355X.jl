@@ -651,6 +651,51 @@ function Base.close(vp::MI355XVolPath)
 end
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# Lights and environment maps in place (hk_scene_update_lights / hk_scene_update_envmap): the scene on the device is edited, not rebuilt
+# ---------------------------------------------------------------------------------------------------------------------------
+"""
+    update_light!(vp, flat_index, light; envmap_index = 0)
+
+Replaces light `flat_index` (0-based, in the `flat_to_light_index` order `flatten_scene` uploads) of the scene `vp` holds on its devices
+by `light`, which must be of the same type.  The library rebuilds the light BVH; films are not cleared.  An `EnvironmentLight` keeps
+pointing at map `envmap_index` of the scene; a textured `Le` cannot be introduced by an update.
+"""
+function update_light!(vp::MI355XVolPath, flat_index::Integer, light; envmap_index::Integer = 0)
+    fl = Flattener(nothing, HkTexture[], Dict{UInt,Int32}(), HkPlSpectrum[], HkEnvmap[], Any[])
+    rec = if light isa Hikari.EnvironmentLight
+        HkLight(HK_LIGHT_ENVIRONMENT, HK_SPEC_RGB, rgba(light.scale), Z3, 0f0, 1f0, Z3, Z3, Z16, Z16, 0f0, 0f0, Z9, Z3, 0f0, Z6, NO_RGBA, 0, Int32(envmap_index))
+    else
+        light_record(fl, light)
+    end
+    isempty(fl.textures) || error("HikariMI355X: update_light! cannot add a texture to the scene")
+    for d in vp.devs
+        d.scene == C_NULL && continue
+        check(ccall((:hk_scene_update_lights, LIB), Int32, (Ptr{Cvoid}, Int32, Int32, Ref{HkLight}), d.scene, Int32(flat_index), Int32(1), rec), "hk_scene_update_lights")
+    end
+    nothing
+end
+
+"""
+    update_envmap!(vp, index; data = nothing, rotation = nothing)
+
+New texels (`Matrix{RGBSpectrum}` of the map's size) and / or a new rotation (`Mat3f`) for environment map `index` (0-based) of the
+scene on the devices; with texels the library builds the `Distribution2D` tables on the device.
+"""
+function update_envmap!(vp::MI355XVolPath, index::Integer; data = nothing, rotation = nothing)
+    texels = data === nothing ? nothing : Array{Hikari.RGBSpectrum}(data)
+    rot = rotation === nothing ? nothing : collect(rowmajor3(rotation))
+    GC.@preserve texels rot begin
+        pd = texels === nothing ? Ptr{Float32}(C_NULL) : Ptr{Float32}(pointer(texels))
+        pr = rot === nothing ? Ptr{Float32}(C_NULL) : pointer(rot)
+        for d in vp.devs
+            d.scene == C_NULL && continue
+            check(ccall((:hk_scene_update_envmap, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Float32}, Ptr{Float32}), d.scene, Int32(index), pd, pr), "hk_scene_update_envmap")
+        end
+    end
+    nothing
+end
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # postprocess! / denoise! / fill_aux_buffers! forwards (postprocess.jl:293-357, denoise.jl:301-376, film.jl:410-483)
 # ---------------------------------------------------------------------------------------------------------------------------
 const TONEMAPS = Dict(nothing => Int32(0), :none => Int32(0), :reinhard => Int32(1), :reinhard_extended => Int32(2), :aces => Int32(3), :uncharted2 => Int32(4), :filmic => Int32(5))
