@@ -19,7 +19,7 @@ static const char* const KNOB_NAMES[] = {
     "HK_MID_LISTS", "HK_MID_PASS_PATHS_M", "HK_NODE_CACHE", "HK_NVDB_DENSE_MB", "HK_OVERLAP", "HK_PIPELINE", "HK_PIPELINE_AFTER", "HK_PIPELINE_MAX_PATHS_M", "HK_PRESELECT",
     "HK_SELECT_MIN_IDLE", "HK_SHADOW_FEED_ROUNDS", "HK_SHADOW_TRACK_BATCH", "HK_SMALL_PASS", "HK_SMALL_PASS_WAVES", "HK_SOBOL_LO_GB", "HK_SOBOL_TABLE_ONLY",
     "HK_STATE_CACHE_GB", "HK_STATE_SLAB", "HK_TICKET_SHARE", "HK_TRACK_ADVANCE", "HK_TRACK_EXTRA_ADVANCE", "HK_TRACK_MIN_PENDING", "HK_TRACK_POOL", "HK_TRACK_REFILL_IDLE",
-    "HK_WALK_POOL", "HK_WALK_REFILL_IDLE", "HK_WALK_SPLIT", "HK_WAVES_PER_CU", "HK_READBACK_PIN", "HK_DEFER_EXTERNAL", "HK_SELECT_POOL", "HK_SMALL_PASS_FUSED", "HK_SMALL_PASS_MERGED", "HK_OCC_SCALE", "HK_ESCAPED_UNROLL", "HK_SHADOW_FINAL", "HK_TRI_PACK", "HK_LEAN_RECORDS"};
+    "HK_WALK_POOL", "HK_WALK_REFILL_IDLE", "HK_WALK_SPLIT", "HK_WAVES_PER_CU", "HK_READBACK_PIN", "HK_DEFER_EXTERNAL", "HK_SELECT_POOL", "HK_SMALL_PASS_FUSED", "HK_SMALL_PASS_MERGED", "HK_OCC_SCALE", "HK_ESCAPED_UNROLL", "HK_SHADOW_FINAL", "HK_TRI_PACK", "HK_LEAN_RECORDS", "HK_VIEW_CACHE"};
 static bool known_knob(const char* name) {
     for (const char* k : KNOB_NAMES)
         if (std::strcmp(k, name) == 0) return true;
@@ -226,6 +226,7 @@ extern "C" int32_t hk_ctx_set_tables(hk_ctx* c, const hk_tables* t) {
     c->tables.rgb2spec_res = res;
     c->tables.rgb2spec_points = c->r2s_points.as<float4>();
     c->have_tables = true;
+    c->tables_epoch++;
     return HK_OK;
 }
 
@@ -266,7 +267,7 @@ extern "C" int32_t hk_stats_reset(hk_ctx* c) {
     }
     c->seconds_trace = c->seconds_total = 0.0;
     c->trace_launches = c->shadow_launches = c->shade_launches = c->media_launches = c->select_launches = 0;
-    c->fused_passes = 0;
+    c->fused_passes = c->view_cache_hits = 0;
     c->have_span = false;
     return HK_OK;
 }
@@ -360,6 +361,7 @@ extern "C" int32_t hk_stats_get(hk_ctx* c, hk_stats* out) {
     out->seconds_select = cls[5];
     out->select_launches = c->select_launches;
     out->fused_passes = c->fused_passes;
+    out->view_cache_hits = c->view_cache_hits;
     {   // SURVEY 8(d) algorithmic bytes over the counted units
         const uint64_t hits_closest = h.hits < h.rays_closest ? h.hits : h.rays_closest;   // shading attributes are fetched once per accepted closest hit
         out->bytes_algorithmic_trace = h.rays_closest * (32 + 16) + 64 * h.nodes + 36 * h.tris + 96 * hits_closest;

@@ -187,10 +187,12 @@ struct hk_ctx {
     DevBuf sobol, cie, r2s_scale, r2s_coeffs, r2s_points, stats;
     DTables tables{};
     bool have_tables = false;
+    unsigned tables_epoch = 0;            // counts hk_ctx_set_tables calls (part of the view-cache key: camera samples and wavelengths come from the tables)
     std::vector<float> h_r2s_scale, h_r2s_coeffs;
     hk::RGB2Spec r2s_host;
     int count_nodes = 0, time_kernels = 0;
     unsigned long long fused_passes = 0;   // passes rendered by k_small_pass (one launch)
+    unsigned long long view_cache_hits = 0;   // passes that kept the camera records of the pass before them (hk_render.cpp: view cache)
     // timing
     std::vector<std::pair<hipEvent_t, hipEvent_t>> trace_events;   // class 0
     std::vector<std::pair<hipEvent_t, hipEvent_t>> class_events[6];  // 1 shadow, 2 shade, 3 other, 4 media, 5 light selection (reported inside the shade class AND on its own)
@@ -331,6 +333,12 @@ struct hk_integrator {
     DPathState st{};
     std::vector<std::unique_ptr<DevBuf>> bufs;
     int st_capacity = 0, st_depth = 0, st_media = -1;   // what the retained path state was allocated for
+    // VIEW CACHE (hk_render.cpp).  cam_gen: the camera generation of this set — ray_o, ray_d and a 4-byte meta word per entry, written by
+    // k_camera alone (null: none wanted, or cam_unfit: it did not fit beside the rest).  view_key: what the camera records, the depth-0
+    // ray counts and the zeroed L that the set holds were generated from; empty unless the last pass on the set kept them and ran to its film.
+    DPathGen cam_gen{};
+    bool cam_unfit = false;
+    std::string view_key;
     bool mid_pass = false;                              // the current pass is a mid-size one of a closed scene (ensure_state): static stride, one stream
     int slab_mode = 0;         // 0: one allocation per array; 1: measuring the slab; 2: carving it
     void* slab_base = nullptr;
@@ -344,6 +352,9 @@ struct hk_integrator {
         DPathState st{};
         std::vector<std::unique_ptr<DevBuf>> bufs;
         int st_capacity = 0, st_depth = 0, st_media = -1;
+        DPathGen cam_gen{};
+        bool cam_unfit = false;
+        std::string view_key;
     };
     std::vector<StateSet> lane_sets;
     void swap_set(StateSet& o) {
@@ -352,6 +363,9 @@ struct hk_integrator {
         std::swap(st_capacity, o.st_capacity);
         std::swap(st_depth, o.st_depth);
         std::swap(st_media, o.st_media);
+        std::swap(cam_gen, o.cam_gen);
+        std::swap(cam_unfit, o.cam_unfit);
+        std::swap(view_key, o.view_key);
     }
 };
 // hk_render.cpp (the sampler parameters of a film; hk_test_sobol / hk_test_camera build the same)

@@ -328,6 +328,9 @@ __device__ __forceinline__ void st_meta(const DPathState& st, const DPathGen& g,
 __device__ __forceinline__ float4 ld_ray_o(const DPathState& st, const DPathGen& g, size_t p, int depth, size_t seg) {
     return stream_ld(&g.ray_o[(depth == 0 && st.const_origin) ? seg : p]);
 }
+// the generation the readers of bounce `depth` take their records from: the camera's for depth 0 (DPathState::gen_cam — gen[0] itself unless
+// the state keeps the camera records across frames), else the ping-pong set that the shading of depth - 1 wrote
+__device__ __forceinline__ DPathGen gen_at(const DPathState& st, int depth) { return depth == 0 ? st.gen_cam : st.gen[depth & 1]; }
 // dense append of a whole record: the position the pushing lanes get inside the segment (count + rank among the pushing lanes)
 struct WavePos {
     int count;  // wave-uniform: entries already in the segment
@@ -488,7 +491,7 @@ __global__ void __launch_bounds__(256) k_sobol_lo_table(DSobol sob, DFrame fr, u
 __device__ __forceinline__ void camera_body(const DPathState& st, const DFrame& fr, const DTables& T, const DFilter& flt, const DCamera& cam, const DSobol& sob, const SegTickets& src) {
     const int total = fr.n_pixels_padded * fr.samples_in_pass;
     const int n_chunks = total >> 6;
-    const DPathGen g0 = st.gen[0];
+    const DPathGen g0 = st.gen_cam;
     HK_FOR_EACH_SEGMENT_FROM(gw, st, src) {
     WavePos out{0};
     const size_t seg = (size_t)gw * st.wave_cap;
@@ -607,7 +610,7 @@ __global__ void __launch_bounds__(HK_TRACE_BLOCK) k_trace(DPathState st, DScene 
     const int lane = lane_id();
     unsigned n_nodes = 0, n_tris = 0, n_casts = 0, n_hits = 0;
     HK_FOR_EACH_WAVE_SEGMENT(gw, st, ticket_ptr(st, depth, TK_TRACE), depth, Q_RAY) {
-    const DPathGen g = st.gen[depth & 1];
+    const DPathGen g = gen_at(st, depth);
     const uint32_t seg = (uint32_t)gw * (uint32_t)st.wave_cap;   // the segment's live rays are entries seg .. seg + n - 1 of this generation
     const int n = *count_ptr(st, depth, Q_RAY, gw);
     WaveQ q_escaped = wq_open(st.escaped_q, st, gw);
@@ -941,7 +944,7 @@ __device__ __forceinline__ void trace_lean_body(const DPathState& st, const DSce
     unsigned n_nodes = 0, n_tris = 0, n_casts = 0, n_hits = 0;
     HK_DBG_DECL
     HK_FOR_EACH_SEGMENT_FROM(gw, st, src) {
-    const DPathGen g = st.gen[depth & 1];
+    const DPathGen g = gen_at(st, depth);
     const uint32_t seg = (uint32_t)gw * (uint32_t)st.wave_cap;   // the rays of this segment: entries seg .. seg + n - 1, read in order (no index queue)
     const int n = *count_ptr(st, depth, Q_RAY, gw);
     WaveQ q_escaped = wq_open(st.escaped_q, st, gw);
@@ -1090,7 +1093,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256, 256), amdgpu_wav
     const int lane = lane_id();
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     unsigned n_coll = 0, n_dda = 0;
-    const DPathGen g = st.gen[depth & 1];   // throughput / scattering vertex are updated IN PLACE in the current generation
+    const DPathGen g = gen_at(st, depth);   // throughput / scattering vertex are updated IN PLACE in the current generation
     const bool ones = depth == 0 && fr.implicit_ones;
     // The wave streams segment after segment (SegStream) WITHOUT draining its lanes in between: the collision count per path is so
     // uneven that a third of the lane-slots of a segment-at-a-time walk sat empty in the segment's tail.  A finished path must be
@@ -1432,7 +1435,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256, 256), amdgpu_wav
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     unsigned n_coll = 0, n_dda = 0;
     HK_DBG_DECL
-    const DPathGen g = st.gen[depth & 1];
+    const DPathGen g = gen_at(st, depth);
     const bool ones = depth == 0 && fr.implicit_ones;
     const DMedium& med = media[0];
     const float a0 = eval_flat(med.sigma_a), s0 = eval_flat(med.sigma_s);
@@ -1721,7 +1724,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256, 256), amdgpu_wav
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     unsigned n_coll = 0, n_dda = 0;
     HK_DBG_DECL
-    const DPathGen g = st.gen[depth & 1];
+    const DPathGen g = gen_at(st, depth);
     const bool ones = depth == 0 && fr.implicit_ones;
     const DMedium& med = media[0];
     const float a0 = eval_flat(med.sigma_a), s0 = eval_flat(med.sigma_s);
@@ -2040,7 +2043,7 @@ __global__ void __launch_bounds__(256) k_scatter(DPathState st, DScene sc, DTabl
     HK_FOR_EACH_WAVE_SEGMENT(gw, st, ticket_ptr(st, depth, TK_SCATTER), depth, Q_SCATTER) {
         const uint32_t* __restrict__ queue = st.scatter_q + (size_t)gw * st.wave_cap;
         const int n = *count_ptr(st, depth, Q_SCATTER, gw);
-        const DPathGen g = st.gen[depth & 1], gn = st.gen[(depth + 1) & 1];
+        const DPathGen g = gen_at(st, depth), gn = st.gen[(depth + 1) & 1];
         const size_t seg = (size_t)gw * st.wave_cap;
         WavePos q_shadow{0}, q_next{0};   // first writer of this depth's shadow records and of the next generation
         for (int base = 0; base < n; base += 64) {
@@ -2216,7 +2219,7 @@ __device__ __forceinline__ void escaped_body(const DPathState& st, const DScene&
     HK_FOR_EACH_SEGMENT_FROM(gw, st, src) {
     const uint32_t* __restrict__ queue = st.escaped_q + (size_t)gw * st.wave_cap;
     const int n = *count_ptr(st, depth, Q_ESCAPED, gw);
-    const DPathGen g = st.gen[depth & 1];
+    const DPathGen g = gen_at(st, depth);
     const bool ones = depth == 0 && implicit_ones;
     int i = lane_id();
     if (UNROLL == 2) {
@@ -2270,7 +2273,7 @@ __global__ void __launch_bounds__(256) k_light_select(DPathState st, DScene sc, 
     const int lane = lane_id();
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     unsigned n_lnodes = 0;
-    const DPathGen g = st.gen[depth & 1];
+    const DPathGen g = gen_at(st, depth);
     const int base_dim = 6 + 7 * depth;
     const int ninf = sc.num_infinite_lights, nbvh = sc.num_bvh_lights;
     const bool has_bvh = nbvh > 0;
@@ -2441,7 +2444,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(BLOCK, BLOCK), amdgpu
     const int lane = lane_id();
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     unsigned n_lnodes = 0;
-    const DPathGen g = st.gen[depth & 1];
+    const DPathGen g = gen_at(st, depth);
     const int base_dim = 6 + 7 * depth;
     const int ninf = sc.num_infinite_lights, nbvh = sc.num_bvh_lights;
     const bool has_bvh = nbvh > 0;
@@ -2668,7 +2671,7 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
     HK_FOR_EACH_SEGMENT_FROM(gw, st, src) {
     const uint32_t* __restrict__ queue = st.mat_q + ((size_t)KIND * st.n_waves + gw) * st.wave_cap;
     const int n = *count_ptr(st, depth, Q_MAT0 + KIND, gw);
-    const DPathGen g = st.gen[depth & 1], gn = st.gen[(depth + 1) & 1];
+    const DPathGen g = gen_at(st, depth), gn = st.gen[(depth + 1) & 1];
     const size_t seg = (size_t)gw * st.wave_cap;
     const bool ones = depth == 0 && fr.implicit_ones;
     // several kinds append to the same shadow-record / next-generation segments: continue from the counts left by the kinds before
@@ -3099,7 +3102,7 @@ __device__ __forceinline__ void trace_shadow_body(const DPathState& st, const DS
     const int DONE = (int)0x80000000;
     unsigned n_nodes = 0, n_tris = 0, n_casts = 0, n_hits = 0, n_sh_casts = 0;
     const int dt = depth + 1;
-    const DPathGen g = st.gen[dt & 1];
+    const DPathGen g = gen_at(st, dt);
     const uint32_t seg = (uint32_t)gw * (uint32_t)st.wave_cap;
     const int n_ray = *count_ptr(st, dt, Q_RAY, gw), n_sh = *count_ptr(st, depth, Q_SHADOW, gw);
     WaveQ q_escaped = wq_open(st.escaped_q, st, gw);
@@ -4527,6 +4530,7 @@ __device__ __forceinline__ void film_tile(const DPathState& st, const DFrame& fr
                     // slots of film padding were never written by k_camera: whatever they hold is converted but never added
                     const S4 lam_ = ld4(&st.lambda_s[slot]);
                     const v3 rgb = spectral_to_rgb_clamped(T, ld4(&st.L[slot]), lam_, pdf_of(lam_), fr.max_component_value);
+                    if (st.view_cache == 1) stream_st(&st.L[slot], s4(0.0f));   // the next pass may keep this one's camera records: its L starts at zero without k_camera
                     const float fw = st.filter_w[slot];
                     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
                     mine[4 * lane + 0] = fw * rgb.x;
@@ -4559,6 +4563,7 @@ __device__ __forceinline__ void film_tile(const DPathState& st, const DFrame& fr
                 const size_t slot = base + j + lane;
                 const S4 lam_ = ld4(&st.lambda_s[slot]);
                 const v3 rgb = spectral_to_rgb_clamped(T, ld4(&st.L[slot]), lam_, pdf_of(lam_), fr.max_component_value);
+                if (st.view_cache == 1) stream_st(&st.L[slot], s4(0.0f));
                 const float fw = st.filter_w[slot];
                 __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
                 mine[4 * lane + 0] = fw * rgb.x;

@@ -156,7 +156,7 @@ PassTraits pass_traits(const hk_scene* sc, const hk_ctx* c, int n_samples, bool 
     return t;
 }
 // the arrays of the path state I->st (capacity, n_waves and wave_cap set), in the order they are carved from the slab (alloc_arr)
-int layout_state(hk_integrator* I, bool media, bool want_split) {
+int layout_state(hk_integrator* I, bool media, bool want_split, bool want_cam) {
     DPathState& s = I->st;
     const size_t P = (size_t)s.capacity, Q = (size_t)s.n_waves * s.wave_cap;
     const int n_cu = I->ctx->n_cu, W = s.n_waves;
@@ -213,6 +213,23 @@ int layout_state(hk_integrator* I, bool media, bool want_split) {
     if (I->slab_mode != 1) HIP_TRY(hipMemset(s.counters, 0, nc * sizeof(int)));
     HIP_TRY(alloc_arr(I, s.seg_list, nc));
     HIP_TRY(alloc_arr(I, s.seg_list_n, (size_t)(I->p.max_depth + 2) * Q_COUNT));
+    // the camera generation of the view cache (lean records: 16 + 16 + 4 B per entry; a pinhole camera touches one ray_o per segment).  Last,
+    // and optional: without the slab an array that cannot be had leaves the set without one (cam_unfit) instead of failing the call.
+    I->cam_gen = DPathGen{};
+    I->cam_unfit = false;
+    if (want_cam) {
+        DPathGen g{};
+        uint32_t* meta32 = nullptr;
+        const size_t n_bufs = I->bufs.size();
+        if (alloc_arr(I, g.ray_o, Q) == hipSuccess && alloc_arr(I, g.ray_d, Q) == hipSuccess && alloc_arr(I, meta32, Q) == hipSuccess) {
+            g.meta = reinterpret_cast<uint2*>(meta32);
+            I->cam_gen = g;
+        } else {
+            (void)hipGetLastError();
+            I->bufs.resize(n_bufs);
+            I->cam_unfit = true;
+        }
+    }
     return HK_OK;
 }
 // W virtual wave segments: every queue is split W ways and a segment is processed by one wave per kernel, so W is independent of each
@@ -280,9 +297,14 @@ int ensure_state(hk_integrator* I, int capacity, const PassTraits& t, hipStream_
         }
     }
     const bool want_split = media && hk::walk_split_mode();
+    // the view cache's camera generation: sets of surface scenes that the context's own stream renders on (a lane's pass never keeps its records)
+    const bool want_cam = !media && !users && hk::knob_on("HK_VIEW_CACHE");
     // the retained state must be of the same flavour: a state allocated for a scene with media has no sel_light (k_light_select would
     // silently not run in a later scene without media), one allocated without HK_WALK_SPLIT has no hand-over queues
-    if (I->st_capacity >= capacity && I->st_depth >= I->p.max_depth && I->st.n_waves == (int)W_want && I->st_media == (media ? 1 : 0) && (!want_split || I->st.wq_a != nullptr)) return HK_OK;
+    if (I->st_capacity >= capacity && I->st_depth >= I->p.max_depth && I->st.n_waves == (int)W_want && I->st_media == (media ? 1 : 0) && (!want_split || I->st.wq_a != nullptr) &&
+        (!want_cam || I->cam_gen.ray_d != nullptr || I->cam_unfit))
+        return HK_OK;
+    I->view_key.clear();   // whatever the set held goes with its arrays
     if (users) HIP_TRY(hipStreamSynchronize(users));   // (a lane's set: its last call may still be running)
     if (!I->bufs.empty()) quiesce(I->ctx);             // the arrays about to be let go (a cached slab is handed on without a device-wide wait)
     I->bufs.clear();
@@ -293,24 +315,39 @@ int ensure_state(hk_integrator* I, int capacity, const PassTraits& t, hipStream_
     s.n_waves = W;
     s.wave_cap = ((chunks + W - 1) / W) * 64;
     if (hk::knob_on("HK_STATE_SLAB")) {   // (0: one allocation per array, nothing cached)
-        I->slab_mode = 1, I->slab_off = 0;
-        if (int e = layout_state(I, media, want_split)) {
-            I->slab_mode = 0;
-            return e;
+        // the camera generation is part of the slab when the slab still fits with it (the pass is never made smaller for its sake):
+        // measured with it first, and once more without when the memory is not there
+        bool cam = want_cam;
+        for (;;) {
+            I->slab_mode = 1, I->slab_off = 0;
+            if (int e = layout_state(I, media, want_split, cam)) {
+                I->slab_mode = 0;
+                return e;
+            }
+            size_t free_b = 0, total_b = 0;
+            const bool known = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
+            if (!known) (void)hipGetLastError();
+            hipError_t he = hipErrorOutOfMemory;
+            if (!(cam && known && I->slab_off > free_b + g_slabs.total(I->ctx->device))) {
+                I->bufs.emplace_back(new DevBuf());
+                he = I->bufs.back()->alloc_slab(I->ctx->device, I->slab_off);
+            }
+            if (he == hipSuccess) break;
+            (void)hipGetLastError();
+            I->bufs.clear();
+            if (!cam) {
+                I->slab_mode = 0;
+                return fail(HK_ERR_DEVICE, "path-state slab allocation failed");
+            }
+            cam = false;
         }
-        I->bufs.emplace_back(new DevBuf());
-        DevBuf* slab = I->bufs.back().get();
-        const hipError_t he = slab->alloc_slab(I->ctx->device, I->slab_off);
-        if (he != hipSuccess) {
-            I->slab_mode = 0;
-            return fail(HK_ERR_DEVICE, "path-state slab allocation failed");
-        }
-        I->slab_base = slab->p;
+        I->slab_base = I->bufs.back()->p;
         I->slab_mode = 2, I->slab_off = 0;
-        const int e = layout_state(I, media, want_split);
+        const int e = layout_state(I, media, want_split, cam);
         I->slab_mode = 0;
         if (e) return e;
-    } else if (int e = layout_state(I, media, want_split))
+        I->cam_unfit = want_cam && !cam;
+    } else if (int e = layout_state(I, media, want_split, want_cam))
         return e;
     I->st_capacity = capacity;
     I->st_depth = I->p.max_depth;
@@ -522,6 +559,14 @@ struct PassCtx {
     hipStream_t s;
     bool piped;
     int first_sample_idx, sample_stride;
+    // VIEW CACHE.  Everything k_camera writes — the depth-0 records, lambda_s, filter_w, the per-segment ray counts, L = 0 — is a pure
+    // function of film size, pixel range, sample range, sampler, filter, camera and the layout of the set; none of it depends on the
+    // scene.  A one-pass frame on the integrator's own set therefore keeps the camera generation apart from the two that the bounces
+    // ping-pong (DPathState::gen_cam), and the next such frame with the same key (view_key_of) does not launch k_camera: a frame
+    // loop that edits a resident scene between frames, an animation under a fixed camera, a rank re-rendering its share of samples.
+    // view_mode 0: off for this call (gen_cam is gen[0]); 1: k_film zeroes the L entries it has read; 2: a hit clears L with a memset.
+    int view_mode = 0;
+    std::string view_key_of() const;
 
     // fn's launches under a pair of events of timing class `cls` (hk_stats_enable_counters bit 1)
     template <class F>
@@ -550,9 +595,20 @@ struct PassCtx {
         return timed(3, [&] { hk::launch_segment_lists(s, I->st, n, dd, qq); });
     }
     int enqueue_depth(ShadowStream& sh, int depth);
-    int enqueue_stages();
+    int enqueue_stages(bool view_hit);
     int enqueue_pass(int k, int done);
 };
+// what the camera records of the pass are a function of, byte for byte (fr and sob hold the pass's fields)
+std::string PassCtx::view_key_of() const {
+    std::string k;
+    auto put = [&k](const void* p, size_t n) { k.append(static_cast<const char*>(p), n); };
+    put(&dc, sizeof dc);   // (make_camera of the caller's hk_camera: all that generate_ray reads)
+    put(&I->filter, sizeof I->filter);
+    const int v[] = {fr.width, fr.height, fr.x0, fr.y0, fr.x1, fr.y1, fr.first_sample, fr.sample_stride, fr.samples_in_pass, sob.log2_spp, sob.n_base4_digits, (int)sob.seed, sob.width,
+                     fr.implicit_ones, I->st.compact, I->st.meta32, I->st.const_origin, I->st.n_waves, I->st.wave_cap, I->st.dynamic_segments, view_mode, (int)c->tables_epoch};
+    put(v, sizeof v);
+    return k;
+}
 // one bounce: traversal, media, escaped rays, light selection, shading per material kind, shadow rays
 int PassCtx::enqueue_depth(ShadowStream& sh, int depth) {
     if (int e = timed(0, [&] { hk::launch_trace(s, c->n_cu, I->st, sc->d, c->tables, fr, depth, dstats); })) return e;
@@ -599,13 +655,18 @@ int PassCtx::enqueue_depth(ShadowStream& sh, int depth) {
     return HK_OK;
 }
 // the pass as launches: the three clears, camera rays, then bounce by bounce (the launchers size their grids from residency: n_cu)
-int PassCtx::enqueue_stages() {
+int PassCtx::enqueue_stages(bool view_hit) {
     HIP_TRY(hipMemsetAsync(I->st.tickets, 0, (size_t)I->st.ticket_rows * HK_TICKET_COLS * HK_TICKET_WAYS * HK_TICKET_STRIDE * sizeof(int), s));
     // queue sizes start every pass at zero: a depth at which no shade / scatter kernel runs (a triangle-free scene lit by an
-    // environment map, say) must not see the ray / shadow counts an earlier render left behind
-    HIP_TRY(hipMemsetAsync(I->st.counters, 0, (size_t)(I->st_depth + 2) * Q_COUNT * I->st.n_waves * sizeof(int), s));
+    // environment map, say) must not see the ray / shadow counts an earlier render left behind.  A view-cache hit keeps row (0, Q_RAY),
+    // the first of the block: the ray counts k_camera wrote.
+    const size_t kept = view_hit ? (size_t)I->st.n_waves : 0;
+    HIP_TRY(hipMemsetAsync(I->st.counters + kept, 0, ((size_t)(I->st_depth + 2) * Q_COUNT * I->st.n_waves - kept) * sizeof(int), s));
     if (I->st.wq_ctl) HIP_TRY(hipMemsetAsync(I->st.wq_ctl, 0, (size_t)(I->st_depth + 2) * 11 * 4 * sizeof(int), s));
-    if (int e = timed(3, [&] { hk::launch_camera(s, c->n_cu, I->st, fr, c->tables, I->filter, dc, sob, -1); })) return e;
+    if (!view_hit) {
+        if (int e = timed(3, [&] { hk::launch_camera(s, c->n_cu, I->st, fr, c->tables, I->filter, dc, sob, -1); })) return e;
+    } else if (view_mode == 2)   // (mode 1: the film kernel of the pass before left L zeroed)
+        HIP_TRY(hipMemsetAsync(I->st.L, 0, (size_t)fr.n_pixels_padded * fr.samples_in_pass * sizeof(float4), s));
     if (int e = lists({{0, Q_RAY}})) return e;
     // Two streams: k_shadow of bounce d touches only its shadow records and L; k_trace of bounce d + 1 touches neither.  The
     // shadow launch goes to a second stream behind the shade kernels, the next traversal starts beside it, and the first stream
@@ -651,16 +712,25 @@ int PassCtx::enqueue_pass(int k, int done) {
     // a small pass of a closed all-matte scene: camera rays and every bounce in ONE launch (k_small_pass), then the film.  It takes no
     // tickets, and every queue size it reads was written before by the same wave: the three clears of enqueue_stages are not for it.
     const bool fused = !c->time_kernels && !piped && hk::launch_small_pass(s, c->n_cu, I->st, sc->d, c->tables, fr, I->filter, dc, sob, I->p.max_depth, sc->kinds_mask, dstats, true, nullptr, 0);
+    // the camera generation of this pass: one of its own where the view cache applies, else generation 0
+    const int vm = fused ? 0 : view_mode;
+    I->st.view_cache = vm;
+    I->st.gen_cam = vm ? I->cam_gen : I->st.gen[0];
+    const std::string view_key = vm ? view_key_of() : std::string();
+    const bool view_hit = vm && I->view_key == view_key;
+    I->view_key.clear();   // (until this pass has run to its film: an error return on the way leaves the set without a key)
     bool film_inline = false;
     if (fused) {
         film_inline = fr.samples_in_pass == 1;   // a one-sample pass adds its paths to the film itself
         (void)hk::launch_small_pass(s, c->n_cu, I->st, sc->d, c->tables, fr, I->filter, dc, sob, I->p.max_depth, sc->kinds_mask, dstats, false, film->accum, film_inline ? (film->f64 ? 2 : 1) : 0);
         c->fused_passes++;
-    } else if (int e = enqueue_stages())
+    } else if (int e = enqueue_stages(view_hit))
         return e;
     if (piped && c->film_chain) HIP_TRY(hipStreamWaitEvent(s, c->ev_film, 0));   // the film sums in call order
     if (!film_inline)
         if (int e = timed(3, [&] { hk::launch_film(s, I->st, fr, c->tables, film->accum, film->f64); })) return e;
+    if (vm) I->view_key = view_key;
+    if (view_hit) c->view_cache_hits++;
     if (piped) {
         HIP_TRY(hipEventRecord(c->ev_film, s));
         c->film_chain = true;
@@ -783,6 +853,12 @@ static int render_tile_now(hk_ctx* c, hk_scene* sc, hk_integrator* I, hk_film* f
     }
     if (int e = detect_camera_medium(s, I, sc, cam, dstats)) return e;
     PassCtx pass{c, sc, I, film, fr, sob, dc, dstats, s, piped, first_sample_idx, sample_stride};
+    // the view cache serves lean records (hk::lean_scene: no kernel rewrites a depth-0 record in place, and the camera medium is none)
+    // of a frame that is ONE pass on the integrator's own set; other layouts, multi-pass frames and lanes render as ever
+    if (!piped && n_samples == S && I->cam_gen.ray_d != nullptr && I->st.meta32 && fr.implicit_ones) {
+        const int mode = hk::knob_int("HK_VIEW_CACHE", 1);   // 0: off, 2: L cleared by a memset instead of by k_film (A/B switches; films bit-identical)
+        pass.view_mode = mode == 2 ? 2 : (mode != 0 ? 1 : 0);
+    }
     for (int done = 0; done < n_samples;) {
         const int k = n_samples - done < S ? n_samples - done : S;
         if (int e = pass.enqueue_pass(k, done)) return e;

@@ -315,6 +315,9 @@ typedef struct hk_stats {
     /* passes rendered as ONE launch (k_small_pass: camera rays and every bounce of a small pass of a closed all-matte scene; the film
        kernel follows).  Their stages are not counted in *_launches. */
     uint64_t fused_passes;
+    /* passes that kept the camera records of the pass before them on the same path state and did not launch k_camera (the view
+       cache: one-pass frames of an unchanged view; HK_VIEW_CACHE=0 turns it off) */
+    uint64_t view_cache_hits;
 } hk_stats;
 
 typedef struct hk_ctx hk_ctx;
