@@ -142,4 +142,5 @@ EXPORTED_SYMBOLS = [
     "hk_ctx_set_option", "hk_ctx_get_option", "hk_trim_cache", "hk_flush", "hk_film_read_rgb_async", "hk_film_read_wait",
     "hk_film_pin_host", "hk_film_unpin_host", "hk_scene_set_transform", "hk_scene_update_materials", "hk_scene_update_lights", "hk_scene_update_envmap",
     "hk_film_update_aux", "hk_film_read_aux", "hk_film_present", "hk_film_present_async",
+    "hk_scene_update_medium", "hk_scene_medium_copy", "hk_test_medium_bricks",
 ]

@@ -46,6 +46,7 @@ def lib():
         "hk_scene_update_materials": ([vp, i32, i32, C.POINTER(A.hk_material)], i32),
         "hk_scene_update_lights": ([vp, i32, i32, C.POINTER(A.hk_light)], i32),
         "hk_scene_update_envmap": ([vp, i32, PF, PF], i32),
+        "hk_scene_update_medium": ([vp, i32, C.POINTER(A.hk_medium)], i32),
         "hk_integrator_create": ([vp, C.POINTER(A.hk_integrator_params), C.POINTER(vp)], i32),
         "hk_integrator_destroy": ([vp], i32),
         "hk_film_create": ([vp, i32, i32, i32, vp, C.POINTER(vp)], i32),
@@ -85,6 +86,8 @@ def lib():
         "hk_test_trace_lean": ([vp, vp, i32, i32, PF, PF, PF, PF, PI, PF], i32),
         "hk_scene_bvh_info": ([vp, PI, PI, PI], i32),
         "hk_scene_light_bvh_copy": ([vp, PI, PF, C.POINTER(C.c_uint32)], i32),
+        "hk_scene_medium_copy": ([vp, i32, PI, PF, C.POINTER(C.c_uint32)], i32),
+        "hk_test_medium_bricks": ([vp, i32, PI, PF], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

@@ -253,7 +253,7 @@ struct hk_scene {
     int n_materials = 0;
     int bvh_nodes = 0, bvh_leaf_tris = 0, bvh_depth = 0;
     hk::LightBVH lbvh;
-    // ---- in-place edits (hk_scene_set_transform, hk_scene_update_materials, hk_scene_update_lights, hk_scene_update_envmap) ----
+    // ---- in-place edits (hk_scene_set_transform, hk_scene_update_materials, hk_scene_update_lights, hk_scene_update_envmap, hk_scene_update_medium) ----
     std::vector<hk_material> h_materials;   // the records as created / last updated: what an update is checked against
     std::vector<hk_light> h_lights;         // likewise; the light BVH is rebuilt from these
     std::vector<DEnvMap> h_envmaps;         // the device records as uploaded (sizes and table pointers; marg_func_int and rot may be stale)
@@ -276,6 +276,15 @@ struct hk_scene {
         hipEvent_t ev = nullptr;
     };
     std::vector<Staging> staging;
+    // ---- hk_scene_update_medium: per medium, the record as created / last updated (what an update is checked against; its pointers
+    // only say which arrays were given and are never followed), the device record as uploaded, and the buffers (in `owned`) it points into
+    struct Medium {
+        hk_medium rec{};
+        DMedium d{};
+        DevBuf *majorant = nullptr, *maj_zero = nullptr, *density = nullptr, *rgb[3] = {nullptr, nullptr, nullptr};
+        DevBuf *nvdb = nullptr, *blocks = nullptr, *bricks = nullptr;   // NanoVDB: these grow with the tree (bricks: empty while they do not fit HK_NVDB_DENSE_MB)
+    };
+    std::vector<Medium> h_media;
     // the arrays the records above point into (texels, spectra, envmap tables, medium grids): freed with the scene, after the staging
     // events below have been waited for (the destructor's body runs before the members go)
     std::vector<std::unique_ptr<DevBuf>> owned;
@@ -294,6 +303,22 @@ struct hk_scene {
 void bake_material(const hk::RGB2Spec& t, const hk_material& m, DMaterial& o);
 bool material_alpha_tested(const hk_material& m);
 void bake_light(const hk::RGB2Spec& r2s, const hk_light& l, DLight& o);   // o: zeroed
+// hk_scene.cpp; hk_scene_update_medium checks, bakes, plans and classifies with the code hk_scene_create runs
+std::string check_medium_record(const hk_medium& m);
+void bake_medium_fields(const hk::RGB2Spec& r2s, const hk_medium& m, DMedium& o);
+struct NvdbPlan {   // what the device holds of a NanoVDB tree besides its bytes
+    int nvb_min[3] = {0, 0, 0}, nvb_dim[3] = {0, 0, 0};   // DMedium::nvb_min / nvb_dim
+    float background = 0.0f;
+    long long total = 0;          // blocks of the table
+    std::vector<uint2> table;     // DMedium::nv_blocks
+    bool bricks = false;          // the halo bricks fit HK_NVDB_DENSE_MB
+    void fill(DMedium& o) const;
+};
+int plan_nanovdb(const hk_medium& m, NvdbPlan& p);   // HK_OK, or the refusal of the tree (fail())
+struct MediaClasses {
+    int media_mask = 0, all_grey = 0, grey_pool = 0, grey_bricks = 0;
+};
+MediaClasses classify_media(const std::vector<DMedium>& dmed, int n_media);
 // entries of the trails / infinite arrays of a scene of n lights (the node array has twice as many: hk::LightTables)
 inline size_t light_table_capacity(int n_lights) { return n_lights > 0 ? (size_t)n_lights : 1; }
 

@@ -51,6 +51,10 @@ void launch_xform_tris(hipStream_t s, const DXform& X, int first, int n, const f
                        float4* leaf);
 void launch_refit_level(hipStream_t s, int begin, int end, DNode* nodes, DQNode* qnodes, const DQGrid& grid, const float4* leaf, const float* pos);
 void launch_envmap_tables(hipStream_t s, const DEnvMap& e, DEnvMap* record);
+// hk_scene_update_medium: majorant grid + zero-cell mask of a Grid / RGB grid / NanoVDB medium, and the NanoVDB halo bricks, from the data `m` points to
+void launch_majorant_grid(hipStream_t s, const DMedium& m);
+void launch_majorant_nanovdb(hipStream_t s, const DMedium& m, const DIndexBox& index_bbox);
+void launch_nvdb_bricks(hipStream_t s, const DMedium& m, size_t n_blocks);
 
 // ---- sub-kernel entry points of the parity tests (hk_test_kernels.h) ----
 void launch_test_trace(hipStream_t s, const DScene& sc, int n, const float* o, const float* d, const float* tmax, float* t, int* prim, float* uv);

@@ -427,4 +427,34 @@ void launch_envmap_tables(hipStream_t s, const DEnvMap& e, DEnvMap* record) {
     hipLaunchKernelGGL(k_envmap_marginal, dim3(1), dim3(64), 0, s, e.nv, e.marg_func, const_cast<float*>(e.marg_cdf), record);
 }
 
+// The tables hk_scene_update_medium derives from the volume data of `m` (a host copy of the record the device will hold: sizes and the
+// pointers to data already enqueued on `s`): the majorant grid into m.majorant, then its zero-cell mask into m.maj_zero.  A cell goes to
+// one wave, or to a block when the mean box holds more than HK_MAJORANT_BLOCK_VOXELS (8192) voxels: 128 per lane and more.
+static int majorant_block_per_cell(double box_voxels) { return box_voxels > (double)knob_int("HK_MAJORANT_BLOCK_VOXELS", 8192) ? 1 : 0; }
+static void majorant_zero_mask(hipStream_t s, const DMedium& m, int ncell) {
+    hipLaunchKernelGGL(k_majorant_zero_mask, dim3((unsigned)(((long long)ncell + 255) / 256)), dim3(256), 0, s, m.majorant, ncell, const_cast<uint32_t*>(m.maj_zero));
+}
+void launch_majorant_grid(hipStream_t s, const DMedium& m) {
+    const int ncell = m.mres[0] * m.mres[1] * m.mres[2];
+    const int per_block = majorant_block_per_cell((double)m.res[0] * m.res[1] * m.res[2] / ncell);
+    const dim3 grid((unsigned)(per_block ? ncell : ((long long)ncell + 3) / 4));
+    with_bool(m.kind == HK_MEDIUM_RGB_GRID, [&](auto RGB) {
+        hipLaunchKernelGGL((k_majorant_grid<decltype(RGB)::value>), grid, dim3(256), 0, s, m, ncell, per_block, const_cast<float*>(m.majorant));
+    });
+    majorant_zero_mask(s, m, ncell);
+}
+void launch_majorant_nanovdb(hipStream_t s, const DMedium& m, const DIndexBox& ib) {
+    const int ncell = m.mres[0] * m.mres[1] * m.mres[2];
+    double box = 1.0;
+    for (int k = 0; k < 3; ++k) box *= ((double)ib.hi[k] - ib.lo[k] + 1.0) / m.mres[k] + 3.0;   // the cell's share of the bounding box and the slop of 1 on both sides
+    const int per_block = majorant_block_per_cell(box);
+    hipLaunchKernelGGL(k_majorant_nanovdb, dim3((unsigned)(per_block ? ncell : ((long long)ncell + 3) / 4)), dim3(256), 0, s, m, ib, ncell, per_block, const_cast<float*>(m.majorant));
+    majorant_zero_mask(s, m, ncell);
+}
+// the halo bricks of every block of m.nv_blocks into m.nv_bricks (n_blocks = the product of m.nvb_dim)
+void launch_nvdb_bricks(hipStream_t s, const DMedium& m, size_t n_blocks) {
+    const unsigned long long n_out = (unsigned long long)n_blocks * 729u;
+    hipLaunchKernelGGL(k_nvdb_bricks, dim3((unsigned)std::min<unsigned long long>((n_out + 255) / 256, 1u << 20)), dim3(256), 0, s, m, n_out, const_cast<float*>(m.nv_bricks));
+}
+
 }  // namespace hk

@@ -87,6 +87,14 @@ void bake_material(const hk::RGB2Spec& t, const hk_material& m, DMaterial& o) {
 // which kernel variants run: hk_scene_create classifies with it, and hk_scene_update_materials refuses a record whose class differs.
 bool material_alpha_tested(const hk_material& m) { return m.kind == HK_MAT_MATTE && (m.rgb[0].tex >= 0 || m.rgb[0].c[3] < 1.0f); }
 
+// what a medium record must satisfy on its own, whoever hands it in (hk_scene_create; hk_scene_update_medium, which builds the majorant itself)
+std::string check_medium_record(const hk_medium& m) {
+    if (m.kind < HK_MEDIUM_HOMOGENEOUS || m.kind > HK_MEDIUM_NANOVDB) return "unknown medium kind";
+    if (m.kind == HK_MEDIUM_RGB_GRID && ((!m.sigma_a_grid && !m.sigma_s_grid) || (m.Le_grid && !m.sigma_a_grid)))   // media.jl:1073-1079
+        return "RGBGridMedium needs sigma_a_grid or sigma_s_grid (and sigma_a_grid when Le_grid is given)";
+    return std::string();
+}
+
 namespace {
 // Checks of a scene description: the arrays, and texture / spectrum / Mix child / area-light / medium / envmap indices.
 // Nothing is allocated before a description has passed.
@@ -146,9 +154,8 @@ std::string validate_desc(const hk_scene_desc& d) {
     }
     for (int i = 0; i < d.n_media; ++i) {
         const hk_medium& m = d.media[i];
-        if (m.kind < HK_MEDIUM_HOMOGENEOUS || m.kind > HK_MEDIUM_NANOVDB) return "unknown medium kind";
-        if (m.kind == HK_MEDIUM_RGB_GRID && ((!m.sigma_a_grid && !m.sigma_s_grid) || (m.Le_grid && !m.sigma_a_grid)))   // media.jl:1073-1079
-            return "RGBGridMedium needs sigma_a_grid or sigma_s_grid (and sigma_a_grid when Le_grid is given)";
+        std::string bad = check_medium_record(m);
+        if (!bad.empty()) return bad;
         if (m.kind != HK_MEDIUM_HOMOGENEOUS && !m.majorant) return "heterogeneous medium without a majorant grid";
     }
     return std::string();
@@ -540,39 +547,55 @@ std::vector<float> nvdb_dense_bricks(const hk_medium& m, const std::vector<uint2
             }
     return bricks;
 }
-int upload_nanovdb(hk_scene* s, const hk_medium& m, DMedium& o) {
-    DevBuf* nb = &s->own();
-    HIP_TRY(nb->upload(m.nvdb_bytes, (size_t)m.nvdb_size));
-    o.nvdb = nb->as<unsigned char>();
-    float bg_probe;
-    if (!nvdb_block_extent(m, bg_probe, o.nvb_min, o.nvb_dim)) return fail(HK_ERR_UNSUPPORTED, "NanoVDB grid with a non-background root tile (4096^3 constant region) is not supported");
-    long long dim[3], total = 1;
+}  // namespace
+// What the device holds of a NanoVDB tree besides its bytes: extent and background of the block table, the table, and whether the halo
+// bricks fit HK_NVDB_DENSE_MB.  Every refusal of a tree is here, for hk_scene_create and hk_scene_update_medium alike.
+int plan_nanovdb(const hk_medium& m, NvdbPlan& p) {
+    if (!m.nvdb_bytes || m.nvdb_size <= 0) return fail(HK_ERR_INVALID, "NanoVDB medium without tree bytes");
+    if (!nvdb_block_extent(m, p.background, p.nvb_min, p.nvb_dim)) return fail(HK_ERR_UNSUPPORTED, "NanoVDB grid with a non-background root tile (4096^3 constant region) is not supported");
+    long long dim[3];
+    p.total = 1;
     for (int k = 0; k < 3; ++k) {
-        dim[k] = o.nvb_dim[k] < 3 ? 3 : o.nvb_dim[k];
-        total *= dim[k];
+        dim[k] = p.nvb_dim[k] < 3 ? 3 : p.nvb_dim[k];
+        p.total *= dim[k];
     }
-    if (total > (1ll << 27) || m.nvdb_size >= (1ll << 32)) {
+    if (p.total > (1ll << 27) || m.nvdb_size >= (1ll << 32)) {
         return fail(HK_ERR_UNSUPPORTED, "NanoVDB grid too large for the device block table (index bbox > 2^27 blocks or buffer >= 4 GiB)");
     }
-    o.nv_background = bg_probe;
-    std::vector<uint2> table;
-    if (!nvdb_block_table(m, o.nvb_min, dim, bg_probe, table)) return fail(HK_ERR_INVALID, "NanoVDB block table: non-background data on the margin (corrupt tree?)");
-    DevBuf* tb = &s->own();
-    HIP_TRY(tb->upload(table.data(), table.size() * sizeof(uint2)));
-    o.nv_blocks = tb->as<uint2>();
-    for (int k = 0; k < 3; ++k) o.nvb_dim[k] = (int)dim[k];
+    if (!nvdb_block_table(m, p.nvb_min, dim, p.background, p.table)) return fail(HK_ERR_INVALID, "NanoVDB block table: non-background data on the margin (corrupt tree?)");
+    for (int k = 0; k < 3; ++k) p.nvb_dim[k] = (int)dim[k];
     size_t budget_mb = 4096;
     if (const char* e = hk::knob("HK_NVDB_DENSE_MB")) budget_mb = (size_t)std::atol(e);
-    const size_t brick_bytes = (size_t)total * 729 * sizeof(float);
-    if (brick_bytes <= budget_mb * (size_t)(1 << 20)) {
-        const std::vector<float> bricks = nvdb_dense_bricks(m, table, dim, bg_probe);
-        DevBuf* bb = &s->own();
-        HIP_TRY(bb->upload(bricks.data(), brick_bytes));
+    p.bricks = (size_t)p.total * 729 * sizeof(float) <= budget_mb * (size_t)(1 << 20);
+    return HK_OK;
+}
+void NvdbPlan::fill(DMedium& o) const {
+    for (int k = 0; k < 3; ++k) o.nvb_min[k] = nvb_min[k], o.nvb_dim[k] = nvb_dim[k];
+    o.nv_background = background;
+}
+namespace {
+int upload_nanovdb(hk_scene* s, const hk_medium& m, DMedium& o, hk_scene::Medium& hm) {
+    NvdbPlan p;
+    if (int e = plan_nanovdb(m, p)) return e;
+    DevBuf* nb = hm.nvdb = &s->own();
+    HIP_TRY(nb->upload(m.nvdb_bytes, (size_t)m.nvdb_size));
+    o.nvdb = nb->as<unsigned char>();
+    p.fill(o);
+    DevBuf* tb = hm.blocks = &s->own();
+    HIP_TRY(tb->upload(p.table.data(), p.table.size() * sizeof(uint2)));
+    o.nv_blocks = tb->as<uint2>();
+    DevBuf* bb = hm.bricks = &s->own();   // (empty while the bricks do not fit: hk_scene_update_medium sizes it when a later tree's do)
+    if (p.bricks) {
+        const long long dim[3] = {p.nvb_dim[0], p.nvb_dim[1], p.nvb_dim[2]};
+        const std::vector<float> bricks = nvdb_dense_bricks(m, p.table, dim, p.background);
+        HIP_TRY(bb->upload(bricks.data(), bricks.size() * sizeof(float)));
         o.nv_bricks = bb->as<float>();
     }
     return HK_OK;
 }
-int bake_medium(hk_scene* s, const hk::RGB2Spec& r2s, const hk_medium& m, DMedium& o) {
+}  // namespace
+// the part of a DMedium that is no pointer into device memory (hk_scene_update_medium bakes with the same)
+void bake_medium_fields(const hk::RGB2Spec& r2s, const hk_medium& m, DMedium& o) {
     o.kind = m.kind;
     o.g = m.g;
     float cf[4];
@@ -591,8 +614,16 @@ int bake_medium(hk_scene* s, const hk::RGB2Spec& r2s, const hk_medium& m, DMediu
     std::memcpy(o.vec, m.vec, 12);
     o.root_off = m.root_offset_1based;
     o.root_table_size = m.root_table_size;
+    if (m.kind == HK_MEDIUM_RGB_GRID) {
+        o.sigma_scale = m.sigma_scale;
+        o.Le_scale = m.Le_scale;
+    }
+}
+namespace {
+int bake_medium(hk_scene* s, const hk::RGB2Spec& r2s, const hk_medium& m, DMedium& o, hk_scene::Medium& hm) {
+    bake_medium_fields(r2s, m, o);
     if (m.kind != HK_MEDIUM_HOMOGENEOUS) {
-        DevBuf* mb = &s->own();
+        DevBuf* mb = hm.majorant = &s->own();
         HIP_TRY(mb->upload(m.majorant, (size_t)m.majorant_res[0] * m.majorant_res[1] * m.majorant_res[2] * 4));
         o.majorant = mb->as<float>();
         // one bit per majorant cell: value exactly 0 (DMedium::maj_zero, majorant_skip_zero)
@@ -600,12 +631,12 @@ int bake_medium(hk_scene* s, const hk::RGB2Spec& r2s, const hk_medium& m, DMediu
         std::vector<uint32_t> zero((ncell + 31) / 32, 0u);
         for (size_t i = 0; i < ncell; ++i)
             if (m.majorant[i] == 0.0f) zero[i >> 5] |= 1u << (i & 31);
-        DevBuf* zb = &s->own();
+        DevBuf* zb = hm.maj_zero = &s->own();
         HIP_TRY(zb->upload(zero.data(), zero.size() * 4));
         o.maj_zero = zb->as<uint32_t>();
     }
     if (m.kind == HK_MEDIUM_GRID) {
-        DevBuf* db = &s->own();
+        DevBuf* db = hm.density = &s->own();
         HIP_TRY(db->upload(m.density, (size_t)m.res[0] * m.res[1] * m.res[2] * 4));
         o.density = db->as<float>();
     }
@@ -615,27 +646,29 @@ int bake_medium(hk_scene* s, const hk::RGB2Spec& r2s, const hk_medium& m, DMediu
         const float4** dst[3] = {&o.rgb_a, &o.rgb_s, &o.rgb_Le};
         for (int g = 0; g < 3; ++g) {
             if (!src[g]) continue;
-            DevBuf* gb = &s->own();
+            DevBuf* gb = hm.rgb[g] = &s->own();
             HIP_TRY(gb->upload(src[g], nvox * 16));
             *dst[g] = gb->as<float4>();
         }
-        o.sigma_scale = m.sigma_scale;
-        o.Le_scale = m.Le_scale;
     }
-    if (m.kind == HK_MEDIUM_NANOVDB) return upload_nanovdb(s, m, o);
+    if (m.kind == HK_MEDIUM_NANOVDB) return upload_nanovdb(s, m, o, hm);
     return HK_OK;
 }
 int upload_media(hk_scene* s, const hk_scene_desc* d, const hk::RGB2Spec& r2s, std::vector<DMedium>& dmed) {
     dmed.resize(d->n_media > 0 ? d->n_media : 1);
     std::memset(dmed.data(), 0, dmed.size() * sizeof(DMedium));
-    for (int i = 0; i < d->n_media; ++i)
-        if (int e = bake_medium(s, r2s, d->media[i], dmed[i])) return e;
+    s->h_media.resize(d->n_media > 0 ? d->n_media : 0);
+    for (int i = 0; i < d->n_media; ++i) {
+        if (int e = bake_medium(s, r2s, d->media[i], dmed[i], s->h_media[i])) return e;
+        s->h_media[i].rec = d->media[i];
+        s->h_media[i].d = dmed[i];
+    }
     HIP_TRY(s->media.upload(dmed.data(), dmed.size() * sizeof(DMedium)));
     return HK_OK;
 }
-struct MediaClasses {
-    int media_mask = 0, all_grey = 0, grey_pool = 0, grey_bricks = 0;
-};
+}  // namespace
+// The classes of a scene's media: they select kernel instantiations and size the integrator's path state, so hk_scene_update_medium
+// refuses an edit that changes one.
 MediaClasses classify_media(const std::vector<DMedium>& dmed, int n_media) {
     MediaClasses D;
     for (int i = 0; i < n_media; ++i) D.media_mask |= 1 << dmed[i].kind;
@@ -650,6 +683,7 @@ MediaClasses classify_media(const std::vector<DMedium>& dmed, int n_media) {
     D.grey_bricks = (D.all_grey && dmed[0].kind == HK_MEDIUM_NANOVDB && dmed[0].nv_bricks != nullptr) ? 1 : 0;
     return D;
 }
+namespace {
 
 void fill_dscene(hk_scene* s, const hk_scene_desc* d, const BvhUpload& bvh, bool all_opaque, int has_escape, const MediaClasses& mc) {
     DScene& D = s->d;

@@ -1,5 +1,6 @@
 // hk_scene_edit.cpp — in-place scene edits: hk_scene_set_transform (device transform + BVH refit), hk_scene_update_materials,
-// hk_scene_update_lights (records + host rebuild of the light BVH) and hk_scene_update_envmap (rotation, texels + device table build).
+// hk_scene_update_lights (records + host rebuild of the light BVH), hk_scene_update_envmap (rotation, texels + device table build) and
+// hk_scene_update_medium (record, volume data + device build of majorant grid, zero-cell mask and NanoVDB bricks).
 #include "hk_host.h"
 
 // ---- in-place scene edits -----------------------------------------------------------------------------------------------------
@@ -19,6 +20,7 @@
 // whenever the scene has no media, whatever the count); k_light_select_pool's LDS copy of the top of the tree is filled per launch from
 // num_bvh_lights.  The infinite list is a function of the kinds alone and stays as uploaded.
 // hk_scene_update_envmap changes texels, tables and rotation of a map of unchanged size: nothing on the host is derived from those.
+// hk_scene_update_medium changes one medium's record and the data behind it; what it leaves valid is said at the entry point below.
 namespace {
 // the transform of the header's arithmetic: m as given, its normal matrix in double, identity => copy
 std::string make_xform(const float* m34, DXform& X) {
@@ -292,5 +294,164 @@ extern "C" int32_t hk_scene_update_envmap(hk_scene* s, int32_t idx, const float*
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(st->ev, c->stream));
+    return HK_OK;
+}
+
+namespace {
+bool all_finite(const float* p, int n) {
+    for (int j = 0; j < n; ++j)
+        if (!std::isfinite(p[j])) return false;
+    return true;
+}
+// what an update may change: everything but the kind, the voxel and majorant resolutions and which RGB grids there are
+std::string check_medium_update(const hk_medium& old, const hk_medium& m) {
+    if (m.kind != old.kind) return "the kind differs from the record it replaces";
+    std::string bad = check_medium_record(m);   // hk_scene_create's own check of a record
+    if (!bad.empty()) return bad;
+    if (!all_finite(&m.g, 1)) return "non-finite g";
+    if (m.kind == HK_MEDIUM_HOMOGENEOUS) return std::string();
+    if (!all_finite(m.bounds_min, 3) || !all_finite(m.bounds_max, 3)) return "non-finite bounds";
+    if (!all_finite(m.render_to_medium, 16) || !all_finite(m.medium_to_render, 16)) return "non-finite transform";
+    if (std::memcmp(m.majorant_res, old.majorant_res, sizeof m.majorant_res) != 0) return "majorant_res cannot change";
+    if (m.kind == HK_MEDIUM_NANOVDB) {
+        if (!all_finite(m.inv_mat, 9) || !all_finite(m.vec, 3)) return "non-finite inv_mat / vec";
+        return std::string();
+    }
+    if (std::memcmp(m.res, old.res, sizeof m.res) != 0) return "res cannot change";
+    if (m.kind == HK_MEDIUM_GRID) return m.density ? std::string() : std::string("GridMedium without density");
+    if (!all_finite(&m.sigma_scale, 1) || !all_finite(&m.Le_scale, 1)) return "non-finite sigma_scale / Le_scale";
+    if (!m.sigma_a_grid != !old.sigma_a_grid || !m.sigma_s_grid != !old.sigma_s_grid || !m.Le_grid != !old.Le_grid)
+        return "an RGB grid cannot appear or disappear (sigma_a_grid / sigma_s_grid / Le_grid)";
+    return std::string();
+}
+void swap_buffers(DevBuf& a, DevBuf& b) {
+    std::swap(a.p, b.p);
+    std::swap(a.bytes, b.bytes);
+    std::swap(a.slab_dev, b.slab_dev);
+}
+size_t staged(size_t bytes) { return (bytes + 255) & ~(size_t)255; }   // every block of a staging buffer starts on a 256-byte boundary
+}  // namespace
+
+// Medium `idx` becomes *mp.  What this leaves valid, and why: the view cache (hk_render.cpp) is off in scenes with media, so no camera
+// record outlives the edit; the medium the camera sits in is found on the device in every pass (k_detect_camera_medium), from the
+// record of that pass; DScene — the media pointer, n_media and the four classes — is passed to every kernel by value at launch and is
+// not touched: the record array keeps its place, and an edit that would change media_mask / all_grey / grey_pool / grey_bricks (they
+// select kernel instantiations and size the path state: classify_media) is refused, as hk_scene_update_materials refuses a change of
+// opacity class.  Everything derived from the volume data — majorant grid, zero-cell mask, halo bricks — is rebuilt from it on the
+// device, to the bits hk_scene_create would be handed or build; the block table is hk_scene_create's host build, uploaded.
+extern "C" int32_t hk_scene_update_medium(hk_scene* s, int32_t idx, const hk_medium* mp) {
+    if (!s || !mp) return fail(HK_ERR_INVALID, "hk_scene_update_medium: null argument");
+    const int NM = (int)s->h_media.size();
+    if (idx < 0 || idx >= NM) return fail(HK_ERR_INVALID, "hk_scene_update_medium: medium index out of range");
+    const hk_medium& m = *mp;
+    hk_scene::Medium& hm = s->h_media[idx];
+    const std::string at = "hk_scene_update_medium: medium " + std::to_string(idx) + ": ";
+    {
+        std::string bad = check_medium_update(hm.rec, m);
+        if (!bad.empty()) return fail(HK_ERR_INVALID, at + bad);
+    }
+    hk_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    KnobScope knobs(&c->knobs);
+    DMedium o = hm.d;   // the pointers stay (a NanoVDB tree's are set below), everything else is baked as hk_scene_create bakes it
+    bake_medium_fields(c->r2s_host, m, o);
+    NvdbPlan plan;
+    if (m.kind == HK_MEDIUM_NANOVDB) {
+        if (plan_nanovdb(m, plan) != HK_OK) return fail(HK_ERR_INVALID, at + g_err);
+        for (const uint2& e : plan.table)   // a leaf the kernels below (and the tracking kernels) read lies inside the bytes given
+            if (e.x != 0u && (long long)e.x - 1 + 96 + 2048 > (long long)m.nvdb_size) return fail(HK_ERR_INVALID, at + "NanoVDB block table: a leaf lies outside nvdb_size (corrupt tree?)");
+        plan.fill(o);
+        o.nv_bricks = plan.bricks ? reinterpret_cast<const float*>(&plan) : nullptr;   // (for the class check; the buffer's address follows)
+    }
+    {   // the classes of the edited scene, by hk_scene_create's code
+        std::vector<DMedium> all(NM);
+        for (int i = 0; i < NM; ++i) all[i] = s->h_media[i].d;
+        all[idx] = o;
+        const MediaClasses mc = classify_media(all, NM);
+        const DScene& D = s->d;
+        if (mc.media_mask != D.media_mask || mc.all_grey != D.all_grey || mc.grey_pool != D.grey_pool || mc.grey_bricks != D.grey_bricks)
+            return fail(HK_ERR_INVALID, at + (mc.grey_bricks != D.grey_bricks ? "the class of the scene's media would change (halo bricks against HK_NVDB_DENSE_MB: grey_bricks)"
+                                                                              : "the class of the scene's media would change (a grey medium turning coloured or the reverse: all_grey / grey_pool)"));
+    }
+    // one staging block: the record, then the data that crosses to the device (voxel grids, or tree bytes and block table)
+    const size_t nvox = (size_t)m.res[0] * m.res[1] * m.res[2];
+    const float* rgb_src[3] = {m.sigma_a_grid, m.sigma_s_grid, m.Le_grid};
+    const size_t b_tree = m.kind == HK_MEDIUM_NANOVDB ? (size_t)m.nvdb_size : 0, b_table = plan.table.size() * sizeof(uint2), b_bricks = plan.bricks ? (size_t)plan.total * 729 * sizeof(float) : 0;
+    size_t total = staged(sizeof(DMedium));
+    if (m.kind == HK_MEDIUM_GRID) total += staged(nvox * 4);
+    if (m.kind == HK_MEDIUM_RGB_GRID)
+        for (int g = 0; g < 3; ++g) total += rgb_src[g] ? staged(nvox * 16) : 0;
+    if (m.kind == HK_MEDIUM_NANOVDB) total += staged(b_tree) + staged(b_table);
+    hk_scene::Staging* st = nullptr;
+    if (int e = acquire_staging(s, total, st)) return e;
+    if (int e = join_lanes(c)) return e;   // noted calls render the old medium; the lanes finish before the stream rewrites it
+    if (m.kind == HK_MEDIUM_NANOVDB) {
+        // a tree that needs more than the buffers hold gets new ones: all are allocated before any is exchanged, and the stream is
+        // waited for before the old ones go (passes already enqueued read them)
+        DevBuf fresh[3];
+        DevBuf* const have[3] = {hm.nvdb, hm.blocks, hm.bricks};
+        const size_t need[3] = {b_tree, b_table, b_bricks};
+        bool grow = false;
+        for (int k = 0; k < 3; ++k)
+            if (have[k]->bytes < need[k]) {
+                HIP_TRY(fresh[k].alloc(need[k]));
+                grow = true;
+            }
+        if (grow) {
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            for (int k = 0; k < 3; ++k)
+                if (fresh[k].p) swap_buffers(*have[k], fresh[k]);
+        }
+        o.nvdb = hm.nvdb->as<unsigned char>();
+        o.nv_blocks = hm.blocks->as<uint2>();
+        o.nv_bricks = plan.bricks ? hm.bricks->as<float>() : nullptr;
+    }
+    char* h = static_cast<char*>(st->host);
+    size_t off = staged(sizeof(DMedium));
+    auto upload = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
+        std::memcpy(h + off, src, bytes);
+        const hipError_t e = hipMemcpyAsync(dst, h + off, bytes, hipMemcpyHostToDevice, c->stream);
+        off += staged(bytes);
+        return e;
+    };
+    if (m.kind == HK_MEDIUM_GRID) HIP_TRY(upload(hm.density->p, m.density, nvox * 4));
+    if (m.kind == HK_MEDIUM_RGB_GRID)
+        for (int g = 0; g < 3; ++g)
+            if (rgb_src[g]) HIP_TRY(upload(hm.rgb[g]->p, rgb_src[g], nvox * 16));
+    if (m.kind == HK_MEDIUM_NANOVDB) {
+        HIP_TRY(upload(hm.nvdb->p, m.nvdb_bytes, b_tree));
+        HIP_TRY(upload(hm.blocks->p, plan.table.data(), b_table));
+    }
+    // the tables derived from the data, behind its copies; then the record that points to them
+    if (m.kind == HK_MEDIUM_GRID || m.kind == HK_MEDIUM_RGB_GRID) hk::launch_majorant_grid(c->stream, o);
+    if (m.kind == HK_MEDIUM_NANOVDB) {
+        DIndexBox ib;
+        for (int k = 0; k < 3; ++k) ib.lo[k] = m.index_bbox_min[k], ib.hi[k] = m.index_bbox_max[k];
+        hk::launch_majorant_nanovdb(c->stream, o, ib);
+        if (plan.bricks) hk::launch_nvdb_bricks(c->stream, o, (size_t)plan.total);
+    }
+    HIP_TRY(hipGetLastError());
+    std::memcpy(h, &o, sizeof o);
+    HIP_TRY(hipMemcpyAsync(s->media.as<DMedium>() + idx, h, sizeof o, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipEventRecord(st->ev, c->stream));
+    hm.rec = m;
+    hm.d = o;
+    return HK_OK;
+}
+
+extern "C" int32_t hk_scene_medium_copy(hk_scene* s, int32_t idx, int32_t* n_cells, float* majorant, uint32_t* zero_mask) {
+    if (!s || !n_cells) return fail(HK_ERR_INVALID, "hk_scene_medium_copy: null argument");
+    if (idx < 0 || idx >= (int)s->h_media.size()) return fail(HK_ERR_INVALID, "hk_scene_medium_copy: medium index out of range");
+    const DMedium& d = s->h_media[idx].d;
+    const size_t ncell = d.majorant ? (size_t)d.mres[0] * d.mres[1] * d.mres[2] : 0;   // (a homogeneous medium has no grid)
+    *n_cells = (int32_t)ncell;
+    if (!ncell || (!majorant && !zero_mask)) return HK_OK;
+    hk_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    KnobScope knobs(&c->knobs);
+    if (int e = join_lanes(c)) return e;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (majorant) HIP_TRY(hipMemcpy(majorant, d.majorant, ncell * 4, hipMemcpyDeviceToHost));
+    if (zero_mask) HIP_TRY(hipMemcpy(zero_mask, d.maj_zero, (ncell + 31) / 32 * 4, hipMemcpyDeviceToHost));
     return HK_OK;
 }

@@ -177,3 +177,18 @@ extern "C" int32_t hk_test_trace_lean(hk_ctx* c, hk_scene* sc, int32_t anyhit, i
     HIP_TRY(hipMemcpy(out_uv2, ouv, 2 * (size_t)n * 4, hipMemcpyDeviceToHost));
     return HK_OK;
 }
+
+extern "C" int32_t hk_test_medium_bricks(hk_scene* s, int32_t idx, int32_t* dims, float* out) {
+    if (!s || !dims) return fail(HK_ERR_INVALID, "hk_test_medium_bricks: null argument");
+    if (idx < 0 || idx >= (int)s->h_media.size()) return fail(HK_ERR_INVALID, "hk_test_medium_bricks: medium index out of range");
+    const DMedium& d = s->h_media[idx].d;
+    for (int k = 0; k < 3; ++k) dims[k] = d.nv_bricks ? d.nvb_dim[k] : 0;
+    if (!d.nv_bricks || !out) return HK_OK;
+    hk_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    KnobScope knobs(&c->knobs);
+    if (int e = join_lanes(c)) return e;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(out, d.nv_bricks, (size_t)d.nvb_dim[0] * d.nvb_dim[1] * d.nvb_dim[2] * 729 * sizeof(float), hipMemcpyDeviceToHost));
+    return HK_OK;
+}

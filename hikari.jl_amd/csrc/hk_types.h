@@ -153,6 +153,11 @@ struct DMedium {
     float inv_mat[9], vec[3];
 };
 
+// the index bounding box of a NanoVDB tree (hk_medium::index_bbox_*, both ends inclusive): the majorant build clips to it
+struct DIndexBox {
+    int lo[3], hi[3];
+};
+
 struct DMediumInterface {
     int material, inside, outside, pad;
 };

@@ -35,6 +35,58 @@ def _base_record(rec, kind, sigma_a, sigma_s, Le, g):
     rec.medium_to_render[:] = _identity16()
 
 
+def _f32_bounds(bounds):
+    return (tuple(float(f32(v)) for v in bounds[0]), tuple(float(f32(v)) for v in bounds[1]))
+
+
+def _checked_bounds(bounds):
+    b = _f32_bounds(bounds)
+    if len(b[0]) != 3 or len(b[1]) != 3 or not np.isfinite(np.array(b, dtype=np.float64)).all():
+        raise ValueError("update: bounds must be two finite points")
+    return b
+
+
+def _checked_transform(transform):
+    m = np.asarray(transform, dtype=f32)
+    if m.shape != (4, 4) or not np.isfinite(m).all():
+        raise ValueError("update: transform must be a finite 4x4 matrix")
+    inv = np.linalg.inv(m.astype(np.float64)).astype(f32)
+    if not np.isfinite(inv).all():
+        raise ValueError("update: transform is singular")
+    return m, inv
+
+
+def _same_res(name, given, kept):
+    if given is not None and tuple(int(v) for v in given) != tuple(kept):
+        raise ValueError("update: %s cannot change in place (%s -> %s)" % (name, tuple(kept), tuple(given)))
+
+
+def flat_spectrum(sp):
+    return sp.c[0] == sp.c[1] == sp.c[2]
+
+
+def is_grey(medium):
+    """Flat sigma_a and sigma_s of a Grid / NanoVDB medium: the class hk_scene_create derives for a scene of one such medium (it selects
+    the grey tracking kernels), which hk_scene_update_medium does not let an edit change."""
+    return medium.kind in (A.HK_MEDIUM_GRID, A.HK_MEDIUM_NANOVDB) and flat_spectrum(medium.sigma_a) and flat_spectrum(medium.sigma_s)
+
+
+class _HostMajorant:
+    """The majorant grid of a heterogeneous medium, built on the host when it is first asked for: hk_scene_create is handed it, the tests
+    hold it against the device build, and hk_scene_update_medium never reads it — an update() only marks it stale."""
+    _majorant = None
+
+    @property
+    def majorant(self):
+        if self._majorant is None:
+            self._majorant = self._build_majorant()
+        return self._majorant
+
+    @majorant.setter
+    def majorant(self, value):
+        self._majorant = value
+
+
 class HomogeneousMedium(Medium):
     """HomogeneousMedium(; σ_a=0.01, σ_s=1, Le=0, g=0)  (media.jl:762-776)"""
     kind = A.HK_MEDIUM_HOMOGENEOUS
@@ -42,8 +94,16 @@ class HomogeneousMedium(Medium):
     def __init__(self, sigma_a=RGBSpectrum(0.01), sigma_s=RGBSpectrum(1.0), Le=RGBSpectrum(0.0), g=0.0):
         self.sigma_a, self.sigma_s, self.Le, self.g = sigma_a, sigma_s, Le, g
 
-    def fill_record(self, rec, keep):
+    def fill_record(self, rec, keep, majorant=True):
         _base_record(rec, self.kind, self.sigma_a, self.sigma_s, self.Le, self.g)
+
+    def update(self, sigma_a=None, sigma_s=None, Le=None, g=None):
+        """New coefficients in place (what hk_scene_update_medium takes of a homogeneous medium)."""
+        if g is not None and not np.isfinite(g):
+            raise ValueError("update: non-finite g")
+        for name, v in (("sigma_a", sigma_a), ("sigma_s", sigma_s), ("Le", Le), ("g", g)):
+            if v is not None:
+                setattr(self, name, v)
 
 
 def build_majorant_grid(density, res):
@@ -65,7 +125,7 @@ def build_majorant_grid(density, res):
     return out
 
 
-class GridMedium(Medium):
+class GridMedium(_HostMajorant, Medium):
     """GridMedium(density; σ_a, σ_s, g, bounds, transform, majorant_res=(16,16,16))  (media.jl:873-935)."""
     kind = A.HK_MEDIUM_GRID
 
@@ -80,7 +140,31 @@ class GridMedium(Medium):
         self.majorant = build_majorant_grid(self.density, self.majorant_res)
         self.max_density = float(self.density.max())
 
-    def fill_record(self, rec, keep):
+    def _build_majorant(self):
+        return build_majorant_grid(self.density, self.majorant_res)
+
+    def update(self, density=None, sigma_a=None, sigma_s=None, g=None, bounds=None, transform=None, majorant_res=None):
+        """New voxels (same shape), coefficients, bounds or medium-to-render transform in place; raises ValueError for what
+        hk_scene_update_medium refuses of the object alone (a changed resolution or majorant resolution, non-finite values)."""
+        _same_res("majorant_res", majorant_res, self.majorant_res)
+        if density is not None:
+            density = np.ascontiguousarray(density, dtype=f32)
+            _same_res("the density resolution", density.shape, self.density.shape)
+        if g is not None and not np.isfinite(g):
+            raise ValueError("update: non-finite g")
+        b = _checked_bounds(bounds) if bounds is not None else None
+        t = _checked_transform(transform) if transform is not None else None
+        if density is not None:
+            self.density, self.majorant, self.max_density = density, None, float(density.max())
+        if b is not None:
+            self.bounds = b
+        if t is not None:
+            self.medium_to_render, self.render_to_medium = t
+        for name, v in (("sigma_a", sigma_a), ("sigma_s", sigma_s), ("g", g)):
+            if v is not None:
+                setattr(self, name, v)
+
+    def fill_record(self, rec, keep, majorant=True):
         _base_record(rec, self.kind, self.sigma_a, self.sigma_s, RGBSpectrum(0.0), self.g)
         rec.bounds_min[:] = self.bounds[0]
         rec.bounds_max[:] = self.bounds[1]
@@ -91,7 +175,8 @@ class GridMedium(Medium):
         keep.append(jl)
         rec.density = jl.ctypes.data_as(A.PF)
         rec.majorant_res[:] = self.majorant_res
-        rec.majorant = self.majorant.ctypes.data_as(A.PF)
+        rec.majorant = self.majorant.ctypes.data_as(A.PF) if majorant else None
+        keep.append(self._majorant)
         rec.max_density = self.max_density
 
 
@@ -118,7 +203,7 @@ def build_rgb_majorant_grid(sigma_a_grid, sigma_s_grid, sigma_scale, grid_size, 
     return out
 
 
-class RGBGridMedium(Medium):
+class RGBGridMedium(_HostMajorant, Medium):
     """RGBGridMedium(; σ_a_grid, σ_s_grid, Le_grid, sigma_scale=1, Le_scale=0, g=0, bounds, transform, majorant_res=(16,16,16))
     (media.jl:1002-1113).  Grids are [nx, ny, nz, 3|4] RGB(A) voxels; an absent σ grid reads as RGBSpectrum(1)."""
     kind = A.HK_MEDIUM_RGB_GRID
@@ -129,15 +214,7 @@ class RGBGridMedium(Medium):
         if Le_grid is not None:
             assert sigma_a_grid is not None, "Le_grid requires σ_a_grid to be provided (following pbrt-v4)"
 
-        def rgba(gd):
-            if gd is None:
-                return None
-            gd = np.asarray(gd, dtype=f32)
-            assert gd.ndim == 4 and gd.shape[3] in (3, 4)
-            if gd.shape[3] == 3:
-                gd = np.concatenate([gd, np.ones(gd.shape[:3] + (1,), f32)], axis=3)
-            return np.ascontiguousarray(gd)
-
+        rgba = self._rgba
         self.sigma_a_grid, self.sigma_s_grid, self.Le_grid = rgba(sigma_a_grid), rgba(sigma_s_grid), rgba(Le_grid)
         shapes = {gd.shape[:3] for gd in (self.sigma_a_grid, self.sigma_s_grid, self.Le_grid) if gd is not None}
         assert len(shapes) == 1, "grids must have the same dimensions"
@@ -149,7 +226,55 @@ class RGBGridMedium(Medium):
         self.majorant_res = tuple(int(v) for v in majorant_res)
         self.majorant = build_rgb_majorant_grid(self.sigma_a_grid, self.sigma_s_grid, self.sigma_scale, self.res, self.majorant_res)
 
-    def fill_record(self, rec, keep):
+    @staticmethod
+    def _rgba(gd):
+        if gd is None:
+            return None
+        gd = np.asarray(gd, dtype=f32)
+        assert gd.ndim == 4 and gd.shape[3] in (3, 4)
+        if gd.shape[3] == 3:
+            gd = np.concatenate([gd, np.ones(gd.shape[:3] + (1,), f32)], axis=3)
+        return np.ascontiguousarray(gd)
+
+    def _build_majorant(self):
+        return build_rgb_majorant_grid(self.sigma_a_grid, self.sigma_s_grid, self.sigma_scale, self.res, self.majorant_res)
+
+    def update(self, sigma_a_grid=None, sigma_s_grid=None, Le_grid=None, sigma_scale=None, Le_scale=None, g=None, bounds=None, transform=None, majorant_res=None):
+        """New voxels of the grids the medium HAS (same shape), scales, g, bounds or transform in place; raises ValueError for a grid the
+        medium was created without, a changed resolution or majorant resolution, and non-finite values."""
+        _same_res("majorant_res", majorant_res, self.majorant_res)
+        grids = {}
+        for name, gd in (("sigma_a_grid", sigma_a_grid), ("sigma_s_grid", sigma_s_grid), ("Le_grid", Le_grid)):
+            if gd is None:
+                continue
+            if getattr(self, name) is None:
+                raise ValueError("update: %s cannot appear in place (the medium was created without it)" % name)
+            gd = np.asarray(gd, dtype=f32)
+            if gd.ndim != 4 or gd.shape[3] not in (3, 4):
+                raise ValueError("update: %s must be [nx, ny, nz, 3 or 4]" % name)
+            _same_res("the grid resolution", gd.shape[:3], self.res)
+            grids[name] = self._rgba(gd)
+        for name, v in (("sigma_scale", sigma_scale), ("Le_scale", Le_scale), ("g", g)):
+            if v is not None and not np.isfinite(v):
+                raise ValueError("update: non-finite %s" % name)
+        b = _checked_bounds(bounds) if bounds is not None else None
+        t = _checked_transform(transform) if transform is not None else None
+        for name, gd in grids.items():
+            setattr(self, name, gd)
+        if sigma_scale is not None:
+            self.sigma_scale = float(f32(sigma_scale))
+        if Le_scale is not None:
+            self.Le_scale = float(f32(Le_scale))
+        if g is not None:
+            self.g = g
+        if b is not None:
+            self.bounds = b
+        if t is not None:
+            self.medium_to_render, self.render_to_medium = t
+        if grids or sigma_scale is not None:
+            self.majorant = None
+
+    def fill_record(self, rec, keep, majorant=True):
         _base_record(rec, self.kind, RGBSpectrum(0.0), RGBSpectrum(0.0), RGBSpectrum(0.0), self.g)
         rec.sigma_scale, rec.Le_scale = self.sigma_scale, self.Le_scale
         rec.bounds_min[:] = self.bounds[0]
@@ -164,7 +289,8 @@ class RGBGridMedium(Medium):
                 keep.append(jl)
                 setattr(rec, name, jl.ctypes.data_as(A.PF))
         rec.majorant_res[:] = self.majorant_res
-        rec.majorant = self.majorant.ctypes.data_as(A.PF)
+        rec.majorant = self.majorant.ctypes.data_as(A.PF) if majorant else None
+        keep.append(self._majorant)
 
 
 # ---- NanoVDB -----------------------------------------------------------------------------------------------
@@ -461,7 +587,7 @@ def nanovdb_to_dense(buffer, meta):
     return dense
 
 
-class NanoVDBMedium(Medium):
+class NanoVDBMedium(_HostMajorant, Medium):
     """NanoVDBMedium(data; bounds, σ_a=0, σ_s=1, g=0, majorant_res=(64,64,64))  (nanovdb.jl:964-1004)."""
     kind = A.HK_MEDIUM_NANOVDB
 
@@ -472,8 +598,48 @@ class NanoVDBMedium(Medium):
         self.buffer, self.meta = build_nanovdb_from_dense(data, origin, extent)
         self.majorant_res = tuple(int(v) for v in majorant_res)
         self.majorant = build_nanovdb_majorant_grid(self.meta, self.bounds, self.majorant_res)
-        self.max_density = float(self.majorant.max())
         self.sigma_a, self.sigma_s, self.g = sigma_a, sigma_s, g
+
+    def _build_majorant(self):
+        return build_nanovdb_majorant_grid(self.meta, self.bounds, self.majorant_res)
+
+    @property
+    def max_density(self):
+        return float(self.majorant.max())
+
+    def update(self, data=None, filepath=None, bounds=None, sigma_a=None, sigma_s=None, g=None, transform=None, majorant_res=None):
+        """A new tree in place — from a dense field (`data`, placed in `bounds` or the bounds the medium has) or from a file (`filepath`,
+        with `transform` as in from_file) — and / or new coefficients.  The tree may be of any size.  Raises ValueError for a changed
+        majorant resolution, both sources at once and non-finite values."""
+        _same_res("majorant_res", majorant_res, self.majorant_res)
+        if data is not None and filepath is not None:
+            raise ValueError("update: give data or filepath, not both")
+        if filepath is None and transform is not None:
+            raise ValueError("update: transform goes with filepath")
+        if filepath is not None and bounds is not None:
+            raise ValueError("update: the bounds of a file come from the file")
+        if g is not None and not np.isfinite(g):
+            raise ValueError("update: non-finite g")
+        b = _checked_bounds(bounds) if bounds is not None else None
+        if data is not None and not np.isfinite(np.asarray(data, dtype=f32)).all():
+            raise ValueError("update: non-finite voxel")
+        if filepath is not None:
+            new = type(self).from_file(filepath, self.sigma_a, self.sigma_s, self.g, transform, self.majorant_res)
+            self.buffer, self.meta, self.bounds = new.buffer, new.meta, new.bounds
+            self.majorant = new._majorant
+        elif data is not None or b is not None:
+            if data is None:
+                if self.meta["root_offset"] != 1:
+                    raise ValueError("update: new bounds for a tree from a file need the voxels (data=...)")
+                nx, ny, nz = self.meta["dense_shape"]
+                data = self.meta["dense"][:nx, :ny, :nz]
+            bb = b if b is not None else self.bounds
+            extent = tuple(float(f32(bb[1][k]) - f32(bb[0][k])) for k in range(3))
+            self.buffer, self.meta = build_nanovdb_from_dense(data, bb[0], extent)
+            self.bounds, self.majorant = bb, None
+        for name, v in (("sigma_a", sigma_a), ("sigma_s", sigma_s), ("g", g)):
+            if v is not None:
+                setattr(self, name, v)
 
     @classmethod
     def from_file(cls, filepath, sigma_a=RGBSpectrum(0.5), sigma_s=RGBSpectrum(10.0), g=0.0, transform=None, majorant_res=(64, 64, 64)):
@@ -493,7 +659,6 @@ class NanoVDBMedium(Medium):
         self.buffer, self.meta = buffer, meta
         self.majorant_res = tuple(int(v) for v in majorant_res)
         self.majorant = build_nanovdb_majorant_grid(meta, self.bounds, self.majorant_res)
-        self.max_density = float(self.majorant.max())
         self.sigma_a, self.sigma_s, self.g = sigma_a, sigma_s, g
         return self
 
@@ -503,14 +668,16 @@ class NanoVDBMedium(Medium):
             raise ValueError("this medium already holds a full file buffer; write self.buffer with zlib instead")
         save_nanovdb(filepath, self.buffer, self.meta)
 
-    def fill_record(self, rec, keep):
+    def fill_record(self, rec, keep, majorant=True):
         _base_record(rec, self.kind, self.sigma_a, self.sigma_s, RGBSpectrum(0.0), self.g)
         m = self.meta
         rec.bounds_min[:] = self.bounds[0]
         rec.bounds_max[:] = self.bounds[1]
         rec.majorant_res[:] = self.majorant_res
-        rec.majorant = self.majorant.ctypes.data_as(A.PF)
-        rec.max_density = self.max_density
+        rec.majorant = self.majorant.ctypes.data_as(A.PF) if majorant else None
+        keep.append(self._majorant)
+        rec.max_density = self.max_density if majorant else 0.0
+        keep.append(self.buffer)
         rec.nvdb_bytes = self.buffer.ctypes.data_as(C.POINTER(C.c_uint8))
         rec.nvdb_size = self.buffer.size
         rec.root_offset_1based, rec.upper_offset_1based = m["root_offset"], m["upper_offset"]

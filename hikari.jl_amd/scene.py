@@ -2,6 +2,7 @@
 `sync` flattens everything into the POD arrays of hk_scene_desc (the job the Julia shim does by walking
 `scene.accel` / `scene.materials` / `scene.lights`)."""
 import ctypes as C
+import inspect
 
 import numpy as np
 
@@ -9,6 +10,7 @@ from . import _abi as A
 from . import geometry as G
 from . import lights as L
 from . import materials as M
+from . import media as MD
 
 f32 = np.float32
 
@@ -91,6 +93,8 @@ class Scene:
         self._keep = None
         self._device = {}           # id(ctx) -> hk_scene handle (owned: released by close() / the next sync())
         self._transforms = {}       # (first_tri, n_tris) -> 3x4 float32: applied to every device scene after hk_scene_create
+        self._stale_media = set()   # media edited by update_medium whose kept record still waits for its host majorant
+        self._media_keep = {}
         self.bounds = None
 
     # ---- push! ---------------------------------------------------------------------------------
@@ -276,6 +280,43 @@ class Scene:
         for h in (getattr(self, "_device", None) or {}).values():
             _lib.check(_lib.lib().hk_scene_update_envmap(h, idx, env_map._jl.ctypes.data_as(A.PF) if data is not None else None,
                                                         rot.ctypes.data_as(A.PF) if rot is not None else None), "hk_scene_update_envmap")
+
+    def update_medium(self, medium, **changes):
+        """New volume data, coefficients, bounds or transform for a medium of this scene (the keywords of the medium's own update()),
+        in the kept description and in every device scene — which builds the majorant grid, its zero-cell mask and the NanoVDB bricks
+        from the data itself (hk_scene_update_medium); the host majorant of `medium` is rebuilt only when a scene is created again."""
+        for idx, m in enumerate(self.media):
+            if m is medium:
+                break
+        else:
+            raise ValueError("update_medium: the medium belongs to no medium interface of this scene")
+        unknown = set(changes) - set(inspect.signature(medium.update).parameters)
+        if unknown:
+            raise ValueError("update_medium: a %s has no %s to change" % (type(medium).__name__, ", ".join(sorted(unknown))))
+        if len(self.media) == 1 and medium.kind in (A.HK_MEDIUM_GRID, A.HK_MEDIUM_NANOVDB):
+            # a scene of ONE medium with flat sigma_a and sigma_s runs the grey kernels: that class cannot change in place
+            after = all(MD.flat_spectrum(changes.get(k) or getattr(medium, k)) for k in ("sigma_a", "sigma_s"))
+            if after != MD.is_grey(medium):
+                raise ValueError("update_medium: a grey medium (flat sigma_a and sigma_s) cannot turn coloured in place, nor a coloured one grey")
+        medium.update(**changes)               # refuses what the library would refuse of the object alone (ValueError)
+        if self._desc is None:
+            return
+        self._stale_media.add(idx)             # the kept record is refilled, with the host majorant, when a scene is created from it
+        keep = []
+        rec = A.hk_medium()
+        medium.fill_record(rec, keep, majorant=False)
+        from . import _lib
+        for h in (getattr(self, "_device", None) or {}).values():
+            _lib.check(_lib.lib().hk_scene_update_medium(h, idx, C.byref(rec)), "hk_scene_update_medium")
+
+    def _refresh_media(self):
+        for idx in sorted(self._stale_media):
+            keep = []
+            rec = A.hk_medium()
+            self.media[idx].fill_record(rec, keep)
+            self._media_keep[idx] = keep
+            self._desc.media[idx] = rec
+        self._stale_media.clear()
 
     def _apply_transforms(self, handle):
         from . import _lib
@@ -579,6 +620,7 @@ class Scene:
             c = (lo + hi) * f32(0.5)
             self.bounds = (lo, hi, c, float(np.linalg.norm(hi - c)))
         self._device = {}
+        self._stale_media, self._media_keep = set(), {}
         return self
 
     def close(self):
@@ -600,6 +642,8 @@ class Scene:
     def desc(self):
         if self._desc is None:
             self.sync()
+        if self._stale_media:
+            self._refresh_media()
         return self._desc
 
     def world_radius(self):

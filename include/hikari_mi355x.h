@@ -391,11 +391,40 @@ int32_t hk_scene_destroy(hk_scene* scene);
  *                 cdf[v][u] = func_int[v] == 0 ? (float)u / (float)nu : c[u] / func_int[v]          (u = 1 .. nu; cdf[v][0] = 0)
  *   marginal      the same over func_int[0 .. nv-1] with nv in place of nu; its integral is marginal_func_int
  * Refused: a null scene, both pointers NULL, idx out of range, a non-finite rotation entry, texels for a map whose tables are not of
- * the texels' resolution (nu != width or nv != height). */
+ * the texels' resolution (nu != width or nv != height).
+ *
+ * hk_scene_update_medium: medium `idx` of hk_scene_desc::media is replaced by *medium.  What may change: sigma_a, sigma_s, Le, g of every
+ * kind (baked as hk_scene_create bakes them); of a Grid / RGB grid medium the voxel data (density, or sigma_a_grid / sigma_s_grid /
+ * Le_grid), sigma_scale, Le_scale, bounds_* and the two transforms; of a NanoVDB medium the tree — of any size: nvdb_bytes, nvdb_size, the
+ * offsets and counts, inv_mat, vec, index_bbox_* — and bounds_*.  `majorant` and `max_density` are NOT read (NULL / 0 will do): the
+ * majorant grid, its zero-cell mask and the NanoVDB halo bricks are built ON THE DEVICE from the data, and are bit for bit what
+ * hk_scene_create is handed by a caller that follows the reference, or builds itself:
+ *   Grid        cell i of r along an axis of n voxels covers the 1-based voxels max(1, floor(i*n/r) + 1) .. min(n, ceil((i+1)*n/r))
+ *               (exact integer arithmetic; media.jl:1459-1493); value = max(0, the largest density in the box)
+ *   RGB grid    the same boxes; value = sigma_scale * (ma + ms) in binary32, ma / ms = max(0, the largest R, G or B of sigma_a_grid /
+ *               sigma_s_grid in the box), 1 for a grid that is absent (media.jl:1122-1183)
+ *   NanoVDB     per axis k the corners bounds_min[k] + (bounds_max[k] - bounds_min[k]) * i / r and ... * (i + 1) / r in binary32
+ *               (product, quotient, sum), both through p -> inv_mat * (p - vec) with every row summed left to right; the inclusive integer
+ *               range [floor(min - 1), ceil(max + 1)] clipped to index_bbox_*; value = max(0, the voxels of the range), a voxel outside
+ *               every leaf reading its tile's or the root's background value (nanovdb.jl:1174-1235)
+ *   mask        bit c set <=> value of cell c is exactly 0;  bricks: every block of the host-built block table with the first plane of
+ *               its +x / +y / +z neighbours, when they fit HK_NVDB_DENSE_MB (as at creation)
+ * Only the voxel grids, or the tree bytes and the block table, cross to the device, through pinned memory owned by the scene; the data is
+ * borrowed for the call.  Grid data and majorant are overwritten in place.  The NanoVDB tree, block table and brick buffers are reused
+ * while the new tree fits them; when one has to GROW, the call waits for the context's stream before the old buffer is released (the
+ * one case in which an edit waits for the device).
+ * Refused: a null pointer, idx out of range, a different kind, a different res (grid kinds) or majorant_res, an RGB grid that appears or
+ * disappears, what hk_scene_create refuses of a medium record (an RGB grid medium without its grids, a NanoVDB tree with a non-background
+ * root tile, too large for the block table, or with data on the table's margin), a leaf outside nvdb_size, non-finite g, bounds,
+ * transforms, scales, inv_mat or vec, and an edit after which the scene's media classes would differ from those it was created with:
+ * a grey medium (flat sigma_a and sigma_s) turning coloured or the reverse, bricks that no longer fit HK_NVDB_DENSE_MB or fit it for
+ * the first time in a scene whose only medium is grey.  The classes select kernels and size the integrator's path state.  Every refusal
+ * of this call is HK_ERR_INVALID. */
 int32_t hk_scene_set_transform(hk_scene* scene, int32_t first_tri, int32_t n_tris, const float* m34);
 int32_t hk_scene_update_materials(hk_scene* scene, int32_t first, int32_t n, const hk_material* materials);
 int32_t hk_scene_update_lights(hk_scene* scene, int32_t first, int32_t n, const hk_light* lights);
 int32_t hk_scene_update_envmap(hk_scene* scene, int32_t idx, const float* data, const float* rotation);
+int32_t hk_scene_update_medium(hk_scene* scene, int32_t idx, const hk_medium* medium);
 
 int32_t hk_integrator_create(hk_ctx* ctx, const hk_integrator_params* params, hk_integrator** out);
 int32_t hk_integrator_destroy(hk_integrator* integ);
@@ -420,7 +449,7 @@ int32_t hk_film_clear(hk_film* film); /* clear!(vp), volpath.jl:108-113 */
  *     following on) are rendered as ONE pass — bit-identical film, a seventh of the time — when the note reaches HK_BATCH_PATHS_M
  *     (64 M paths), when a call comes that does not continue it, or when anything looks: hk_flush, hk_sync, every hk_film_* / hk_stats_* /
  *     hk_*_destroy / hk_ctx_set_option /
- *     hk_scene_set_transform / hk_scene_update_materials / hk_scene_update_lights / hk_scene_update_envmap entry point.  hk_flush enqueues the noted calls without waiting for them.
+ *     hk_scene_set_transform / hk_scene_update_materials / hk_scene_update_lights / hk_scene_update_envmap / hk_scene_update_medium entry point.  hk_flush enqueues the noted calls without waiting for them.
  *     HK_BATCH_PATHS_M=0 (hk_ctx_set_option) turns the noting off.
  * Argument errors are reported by the call itself; a device error of a deferred pass by the call that flushes it — also by the
  * destroy entry points, which still destroy their object. */
@@ -612,6 +641,13 @@ int32_t hk_test_trace_lean(hk_ctx* ctx, hk_scene* scene, int32_t anyhit, int32_t
 int32_t hk_scene_bvh_info(hk_scene* scene, int32_t* n_nodes, int32_t* n_leaf_tris, int32_t* max_depth);
 int32_t hk_scene_light_bvh_copy(hk_scene* scene, int32_t* n_nodes, float* nodes_out /* 16 floats per node */,
                                 uint32_t* bit_trails /* n_lights */);
+
+/* The majorant grid (n_cells floats, index x + rx*(y + ry*z)) and the zero-cell mask ((n_cells + 31) / 32 words, bit c of the mask = cell c)
+   of medium `idx` as the device holds them; waits for the context's stream.  Either array may be NULL; n_cells = 0 for a homogeneous medium. */
+int32_t hk_scene_medium_copy(hk_scene* scene, int32_t idx, int32_t* n_cells, float* majorant, uint32_t* zero_mask);
+/* The halo bricks of NanoVDB medium `idx` as the device holds them: dims[3] = the block table's extent (all 0 when the medium has no
+   bricks), out (NULL: only the extent) = dims[0]*dims[1]*dims[2] bricks of 729 floats, block (bx, by, bz) at bz + dims[2]*(by + dims[1]*bx). */
+int32_t hk_test_medium_bricks(hk_scene* scene, int32_t idx, int32_t* dims, float* out);
 
 #ifdef __cplusplus
 }

@@ -651,7 +651,7 @@ function Base.close(vp::MI355XVolPath)
 end
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# Lights and environment maps in place (hk_scene_update_lights / hk_scene_update_envmap): the scene on the device is edited, not rebuilt
+# Lights, environment maps and media in place (hk_scene_update_lights / hk_scene_update_envmap / hk_scene_update_medium): the scene on the device is edited, not rebuilt
 # ---------------------------------------------------------------------------------------------------------------------------
 """
     update_light!(vp, flat_index, light; envmap_index = 0)
@@ -690,6 +690,25 @@ function update_envmap!(vp::MI355XVolPath, index::Integer; data = nothing, rotat
         for d in vp.devs
             d.scene == C_NULL && continue
             check(ccall((:hk_scene_update_envmap, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Float32}, Ptr{Float32}), d.scene, Int32(index), pd, pr), "hk_scene_update_envmap")
+        end
+    end
+    nothing
+end
+
+"""
+    update_medium!(vp, index, medium)
+
+Medium `index` (0-based, in the order `flatten_scene` uploads `scene.media`) of the scene on the devices becomes `medium`, an object of the
+same type, voxel resolution and majorant resolution: a new density field, new coefficients, new bounds, a new NanoVDB tree of any size.
+The library builds the majorant grid (and the NanoVDB bricks) on the device from the data; the `majorant_grid` of `medium` is not read.
+"""
+function update_medium!(vp::MI355XVolPath, index::Integer, medium)
+    fl = Flattener(nothing, HkTexture[], Dict{UInt,Int32}(), HkPlSpectrum[], HkEnvmap[], Any[])
+    rec = medium_record(fl, medium)
+    GC.@preserve fl begin
+        for d in vp.devs
+            d.scene == C_NULL && continue
+            check(ccall((:hk_scene_update_medium, LIB), Int32, (Ptr{Cvoid}, Int32, Ref{HkMedium}), d.scene, Int32(index), rec), "hk_scene_update_medium")
         end
     end
     nothing
