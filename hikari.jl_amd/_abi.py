@@ -142,5 +142,13 @@ EXPORTED_SYMBOLS = [
     "hk_ctx_set_option", "hk_ctx_get_option", "hk_trim_cache", "hk_flush", "hk_film_read_rgb_async", "hk_film_read_wait",
     "hk_film_pin_host", "hk_film_unpin_host", "hk_scene_set_transform", "hk_scene_update_materials", "hk_scene_update_lights", "hk_scene_update_envmap",
     "hk_film_update_aux", "hk_film_read_aux", "hk_film_present", "hk_film_present_async",
-    "hk_scene_update_medium", "hk_scene_medium_copy", "hk_test_medium_bricks",
+    "hk_scene_update_medium", "hk_scene_medium_copy", "hk_test_medium_bricks", "hk_scene_set_vertices", "hk_scene_bvh_cost", "hk_scene_bvh_copy",
 ]
+
+# prototypes (argtypes, restype) of the geometry edit and the tree introspection, in the header's order; _lib.py installs them
+_VP, _I32, _PI32, _PD = C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double)
+PROTOTYPES = {
+    "hk_scene_set_vertices": ([_VP, _I32, _I32, PF, PF, PF, PF], _I32),
+    "hk_scene_bvh_cost": ([_VP, _PD, _PD], _I32),
+    "hk_scene_bvh_copy": ([_VP, _PI32, PF, _PI32], _I32),
+}

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "bvh_build.h"
+#include "hk_edit_host.h"
 #include "hikari_mi355x.h"
 #include "hk_launch.h"
 #include "hk_nanovdb.h"
@@ -253,17 +254,20 @@ struct hk_scene {
     int n_materials = 0;
     int bvh_nodes = 0, bvh_leaf_tris = 0, bvh_depth = 0;
     hk::LightBVH lbvh;
-    // ---- in-place edits (hk_scene_set_transform, hk_scene_update_materials, hk_scene_update_lights, hk_scene_update_envmap, hk_scene_update_medium) ----
+    // ---- in-place edits (hk_scene_set_transform, hk_scene_set_vertices, hk_scene_update_materials, hk_scene_update_lights, hk_scene_update_envmap, hk_scene_update_medium) ----
     std::vector<hk_material> h_materials;   // the records as created / last updated: what an update is checked against
     std::vector<hk_light> h_lights;         // likewise; the light BVH is rebuilt from these
     std::vector<DEnvMap> h_envmaps;         // the device records as uploaded (sizes and table pointers; marg_func_int and rot may be stale)
     int n_textures = 0, n_spectra = 0;
     std::vector<int> level_start;           // breadth-first node levels: level L is [level_start[L], level_start[L + 1])
-    DevBuf base_pos, base_nrm, base_tan, slot_of_prim;   // geometry as created and the leaf slot of every triangle (first transform)
+    DevBuf base_pos, base_nrm, base_tan, slot_of_prim;   // base geometry (as created / last hk_scene_set_vertices) and the leaf slot of every triangle (first transform or new vertices)
+    DevBuf vertex_stage;                    // hk_scene_set_vertices: the uploaded range and its interval table, read by k_set_tris (grows with the largest range)
+    DevBuf cost_partial;                    // hk_scene_bvh_cost: the per-block sums of k_bvh_cost (first call)
+    double cost_created = 0.0;              // the tree cost of the tree as built (hk_scene_bvh_cost)
     bool have_base = false;
     bool qnodes_built = false;              // s->qnodes holds a quantised tree (D.qnodes is null while no grid is known to contain it)
     enum { XF_BLOCK = 1024 };
-    std::vector<float> block_box;           // deep trees: lo[3] hi[3] of the base positions of every XF_BLOCK triangles
+    std::vector<float> block_box;           // deep trees: lo[3] hi[3] (or a superset) of the base positions of every XF_BLOCK triangles
     struct Xf {
         int end;
         bool identity;

@@ -50,6 +50,11 @@ void launch_slot_of_prim(hipStream_t s, const float4* leaf, int n, int* slot_of_
 void launch_xform_tris(hipStream_t s, const DXform& X, int first, int n, const float* bp, const float* bn, const float* bt, const int* slot_of_prim, float* pos, float* nrm, float* tan, float* shade,
                        float4* leaf);
 void launch_refit_level(hipStream_t s, int begin, int end, DNode* nodes, DQNode* qnodes, const DQGrid& grid, const float4* leaf, const float* pos);
+// hk_scene_set_vertices: one pass over the uploaded range (base copies, transform, every copy of the geometry, leaf slots)
+void launch_set_tris(hipStream_t s, const DSetTris& A);
+// hk_scene_bvh_cost: partial[b] = the cost terms of nodes [256 b, 256 b + 256) (bvh_cost_blocks(n) of them)
+inline int bvh_cost_blocks(int n_nodes) { return (n_nodes + 255) / 256; }
+void launch_bvh_cost(hipStream_t s, const DNode* nodes, int n, double* partial);
 void launch_envmap_tables(hipStream_t s, const DEnvMap& e, DEnvMap* record);
 // hk_scene_update_medium: majorant grid + zero-cell mask of a Grid / RGB grid / NanoVDB medium, and the NanoVDB halo bricks, from the data `m` points to
 void launch_majorant_grid(hipStream_t s, const DMedium& m);

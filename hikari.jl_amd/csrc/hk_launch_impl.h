@@ -420,6 +420,10 @@ void launch_xform_tris(hipStream_t s, const DXform& X, int first, int n, const f
 void launch_refit_level(hipStream_t s, int begin, int end, DNode* nodes, DQNode* qnodes, const DQGrid& grid, const float4* leaf, const float* pos) {
     hipLaunchKernelGGL(k_refit_level, dim3(grid_for(end - begin, 256, 8192)), dim3(256), 0, s, begin, end, nodes, qnodes, grid, leaf, pos);
 }
+void launch_set_tris(hipStream_t s, const DSetTris& A) { hipLaunchKernelGGL(k_set_tris, dim3(grid_for(A.n, 256, 8192)), dim3(256), 0, s, A); }
+void launch_bvh_cost(hipStream_t s, const DNode* nodes, int n, double* partial) {
+    hipLaunchKernelGGL(k_bvh_cost, dim3((unsigned)bvh_cost_blocks(n)), dim3(256), 0, s, nodes, n, partial);
+}
 // the Distribution2D tables of map `e` (a host copy of the record: sizes and table pointers) from its texels; `record` is the device record
 void launch_envmap_tables(hipStream_t s, const DEnvMap& e, DEnvMap* record) {
     hipLaunchKernelGGL(k_envmap_rows, dim3((e.nv + 63) / 64), dim3(64), 0, s, e.data, e.nu, e.nv, const_cast<float*>(e.cond_func), const_cast<float*>(e.cond_cdf),

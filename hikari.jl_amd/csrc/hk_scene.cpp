@@ -248,6 +248,10 @@ int upload_bvh(hk_scene* s, const hk_scene_desc* d, const std::vector<uint8_t>& 
     const std::vector<DNode> dn = pack_nodes(bvh);
     const std::vector<float4> lt = pack_leaf_tris(bvh, d, mi_opaque);
     HIP_TRY(s->nodes.upload(dn.data(), dn.size() * sizeof(DNode)));
+    s->cost_created = hk::tree_cost(bvh.nodes.size(), [&](size_t i, float lo[2][3], float hi[2][3], int& c0, int& c1) {   // hk_scene_bvh_cost: of the float boxes as uploaded
+        hk_unpack_node_boxes(dn[i], lo, hi);
+        c0 = dn[i].c0, c1 = dn[i].c1;
+    });
     // a deep tree gets the quantised copy, read by the lean traversal kernels' deep-tree instantiations (HK_QNODES=0: off)
     // (shallow trees gain nothing: their any-hit kernel with the nodes beyond its LDS cache read from a quantised array — measured,
     //  Cornell shadow class + 1.7 %, two-spheres + 0.7 % — is bound by instruction issue, and the conversions are instructions)

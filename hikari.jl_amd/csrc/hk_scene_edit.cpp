@@ -1,6 +1,7 @@
-// hk_scene_edit.cpp — in-place scene edits: hk_scene_set_transform (device transform + BVH refit), hk_scene_update_materials,
-// hk_scene_update_lights (records + host rebuild of the light BVH), hk_scene_update_envmap (rotation, texels + device table build) and
-// hk_scene_update_medium (record, volume data + device build of majorant grid, zero-cell mask and NanoVDB bricks).
+// hk_scene_edit.cpp — in-place scene edits: hk_scene_set_transform (device transform + BVH refit), hk_scene_set_vertices (new base
+// geometry of a triangle range in one device pass + BVH refit), hk_scene_update_materials, hk_scene_update_lights (records + host
+// rebuild of the light BVH), hk_scene_update_envmap (rotation, texels + device table build) and hk_scene_update_medium (record, volume
+// data + device build of majorant grid, zero-cell mask and NanoVDB bricks); hk_scene_bvh_cost / hk_scene_bvh_copy read the refit tree back.
 #include "hk_host.h"
 
 // ---- in-place scene edits -----------------------------------------------------------------------------------------------------
@@ -85,6 +86,48 @@ bool quant_grid(const hk_scene* s, DQGrid& g) {
     }
     return true;
 }
+// the base copies of the geometry and the leaf slot of every triangle (first edit of the geometry only: an unedited scene pays nothing)
+int ensure_base(hk_scene* s) {
+    if (s->have_base) return HK_OK;
+    hk_ctx* c = s->ctx;
+    DScene& D = s->d;
+    const int T = D.n_tris;
+    HIP_TRY(s->base_pos.alloc((size_t)T * 36));
+    HIP_TRY(hipMemcpyAsync(s->base_pos.p, D.positions, (size_t)T * 36, hipMemcpyDeviceToDevice, c->stream));
+    if (D.normals) {
+        HIP_TRY(s->base_nrm.alloc((size_t)T * 36));
+        HIP_TRY(hipMemcpyAsync(s->base_nrm.p, D.normals, (size_t)T * 36, hipMemcpyDeviceToDevice, c->stream));
+    }
+    if (D.tangents) {
+        HIP_TRY(s->base_tan.alloc((size_t)T * 36));
+        HIP_TRY(hipMemcpyAsync(s->base_tan.p, D.tangents, (size_t)T * 36, hipMemcpyDeviceToDevice, c->stream));
+    }
+    HIP_TRY(s->slot_of_prim.alloc((size_t)T * 4));
+    hk::launch_slot_of_prim(c->stream, D.leaf_tris, s->bvh_leaf_tris, s->slot_of_prim.as<int>());
+    HIP_TRY(hipGetLastError());
+    s->have_base = true;
+    return HK_OK;
+}
+// every box of the unchanged topology from D.positions, deepest level first; the quantised copy on a grid that holds the edited tree,
+// or the float nodes when none is known to
+int refit_tree(hk_scene* s) {
+    hk_ctx* c = s->ctx;
+    DScene& D = s->d;
+    DQGrid grid{};
+    DQNode* qn = nullptr;
+    if (s->qnodes_built) {
+        if (quant_grid(s, grid)) {
+            qn = s->qnodes.as<DQNode>();
+            for (int k = 0; k < 3; ++k) D.q_base[k] = grid.base[k], D.q_cell[k] = grid.cell[k];
+        }
+        D.qnodes = qn;   // null: no grid is known to hold the moved tree, the traversal reads the float nodes (same hits)
+    }
+    for (int L = (int)s->level_start.size() - 2; L >= 0; --L) {   // nothing to do when the root is a leaf
+        hk::launch_refit_level(c->stream, s->level_start[L], s->level_start[L + 1], s->nodes.as<DNode>(), qn, grid, D.leaf_tris, D.positions);
+        HIP_TRY(hipGetLastError());
+    }
+    return HK_OK;
+}
 }  // namespace
 
 extern "C" int32_t hk_scene_set_transform(hk_scene* s, int32_t first_tri, int32_t n_tris, const float* m34) {
@@ -102,22 +145,7 @@ extern "C" int32_t hk_scene_set_transform(hk_scene* s, int32_t first_tri, int32_
     KnobScope knobs(&c->knobs);
     if (int e = join_lanes(c)) return e;   // noted calls render the scene as it was; the lanes finish before the stream rewrites it
     DScene& D = s->d;
-    if (!s->have_base) {   // the arrays as created, and the leaf slot of every triangle (first edit only: an unedited scene pays nothing)
-        HIP_TRY(s->base_pos.alloc((size_t)T * 36));
-        HIP_TRY(hipMemcpyAsync(s->base_pos.p, D.positions, (size_t)T * 36, hipMemcpyDeviceToDevice, c->stream));
-        if (D.normals) {
-            HIP_TRY(s->base_nrm.alloc((size_t)T * 36));
-            HIP_TRY(hipMemcpyAsync(s->base_nrm.p, D.normals, (size_t)T * 36, hipMemcpyDeviceToDevice, c->stream));
-        }
-        if (D.tangents) {
-            HIP_TRY(s->base_tan.alloc((size_t)T * 36));
-            HIP_TRY(hipMemcpyAsync(s->base_tan.p, D.tangents, (size_t)T * 36, hipMemcpyDeviceToDevice, c->stream));
-        }
-        HIP_TRY(s->slot_of_prim.alloc((size_t)T * 4));
-        hk::launch_slot_of_prim(c->stream, D.leaf_tris, s->bvh_leaf_tris, s->slot_of_prim.as<int>());
-        HIP_TRY(hipGetLastError());
-        s->have_base = true;
-    }
+    if (int e = ensure_base(s)) return e;
     hk::launch_xform_tris(c->stream, X, first_tri, n_tris, s->base_pos.as<float>(), D.normals ? s->base_nrm.as<float>() : nullptr, D.tangents ? s->base_tan.as<float>() : nullptr,
                           s->slot_of_prim.as<int>(), s->positions.as<float>(), D.normals ? s->normals.as<float>() : nullptr, D.tangents ? s->tangents.as<float>() : nullptr,
                           D.tri_shade ? s->tri_shade.as<float>() : nullptr, s->leaf_tris.as<float4>());
@@ -139,19 +167,7 @@ extern "C" int32_t hk_scene_set_transform(hk_scene* s, int32_t first_tri, int32_
         std::memcpy(x.m, m34, sizeof x.m);
         s->xf[a] = x;
     }
-    DQGrid grid{};
-    DQNode* qn = nullptr;
-    if (s->qnodes_built) {
-        if (quant_grid(s, grid)) {
-            qn = s->qnodes.as<DQNode>();
-            for (int k = 0; k < 3; ++k) D.q_base[k] = grid.base[k], D.q_cell[k] = grid.cell[k];
-        }
-        D.qnodes = qn;   // null: no grid is known to hold the moved tree, the traversal reads the float nodes (same hits)
-    }
-    for (int L = (int)s->level_start.size() - 2; L >= 0; --L) {   // deepest level first; nothing to do when the root is a leaf
-        hk::launch_refit_level(c->stream, s->level_start[L], s->level_start[L + 1], s->nodes.as<DNode>(), qn, grid, D.leaf_tris, D.positions);
-        HIP_TRY(hipGetLastError());
-    }
+    if (int e = refit_tree(s)) return e;
     return HK_OK;
 }
 
@@ -453,5 +469,140 @@ extern "C" int32_t hk_scene_medium_copy(hk_scene* s, int32_t idx, int32_t* n_cel
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (majorant) HIP_TRY(hipMemcpy(majorant, d.majorant, ncell * 4, hipMemcpyDeviceToHost));
     if (zero_mask) HIP_TRY(hipMemcpy(zero_mask, d.maj_zero, (ncell + 31) / 32 * 4, hipMemcpyDeviceToHost));
+    return HK_OK;
+}
+
+// New base geometry for triangles [first_tri, first_tri + n_tris).  What this leaves valid: everything hk_scene_set_transform leaves
+// valid (the header of this file: topology, opacity bits, kinds and the light set are untouched), and the transform intervals
+// hk_scene::xf — the new base is put under the transform each triangle is under.  hk_scene::block_box follows the new positions (a
+// superset where the range covers a block partly), so quant_grid still proves its grid.  The one wait for the device: a range larger
+// than any before grows the device-side staging block, and hipFree of the old one waits for the kernels that read it.
+extern "C" int32_t hk_scene_set_vertices(hk_scene* s, int32_t first_tri, int32_t n_tris, const float* positions, const float* normals, const float* tangents, const float* uvs) {
+    if (!s || !positions) return fail(HK_ERR_INVALID, "hk_scene_set_vertices: null argument");
+    const int T = s->d.n_tris;
+    if (T <= 0) return fail(HK_ERR_INVALID, "hk_scene_set_vertices: the scene has no triangles");
+    if (first_tri < 0 || n_tris < 1 || (int64_t)first_tri + n_tris > T) return fail(HK_ERR_INVALID, "hk_scene_set_vertices: triangle range outside the scene");
+    DScene& D = s->d;
+    if (normals && !D.normals) return fail(HK_ERR_INVALID, "hk_scene_set_vertices: normals for a scene created without normals");
+    if (tangents && !D.tangents) return fail(HK_ERR_INVALID, "hk_scene_set_vertices: tangents for a scene created without tangents");
+    if (uvs && !D.uvs) return fail(HK_ERR_INVALID, "hk_scene_set_vertices: uvs for a scene created without uvs");
+    hk_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    KnobScope knobs(&c->knobs);
+    // the transforms in force on the range, with the normal matrices k_set_tris applies
+    const int a = first_tri, e = first_tri + n_tris;
+    std::vector<int> iv_start;
+    std::vector<DXform> iv_xf;
+    for (auto it = std::prev(s->xf.upper_bound(a)); it != s->xf.end() && it->first < e; ++it) {
+        DXform X{};
+        const std::string bad = make_xform(it->second.m, X);   // (accepted once by hk_scene_set_transform)
+        if (!bad.empty()) return fail(HK_ERR_INVALID, bad);
+        iv_start.push_back(it->first);
+        iv_xf.push_back(X);
+    }
+    // one staging block: interval starts, transforms, then the arrays given
+    const size_t n = (size_t)n_tris;
+    const size_t o_start = 0, o_xf = o_start + staged(iv_start.size() * sizeof(int)), o_pos = o_xf + staged(iv_xf.size() * sizeof(DXform));
+    const size_t o_nrm = o_pos + staged(n * 36), o_tan = o_nrm + (normals ? staged(n * 36) : 0), o_uv = o_tan + (tangents ? staged(n * 36) : 0);
+    const size_t total = o_uv + (uvs ? staged(n * 24) : 0);
+    hk_scene::Staging* st = nullptr;
+    if (int err = acquire_staging(s, total, st)) return err;
+    char* h = static_cast<char*>(st->host);
+    std::vector<float> fresh;   // bounds of the new positions per XF_BLOCK triangles (scenes with quantised nodes)
+    if (!hk::stage_positions(positions, first_tri, n_tris, reinterpret_cast<float*>(h + o_pos), s->block_box.empty() ? 0 : hk_scene::XF_BLOCK, fresh))
+        return fail(HK_ERR_INVALID, "hk_scene_set_vertices: non-finite position");
+    if (s->vertex_stage.bytes < total) HIP_TRY(s->vertex_stage.alloc(total));   // (before anything of the scene changes)
+    if (int err = join_lanes(c)) return err;   // noted calls render the mesh as it was; the lanes finish before the stream rewrites it
+    if (int err = ensure_base(s)) return err;
+    std::memcpy(h + o_start, iv_start.data(), iv_start.size() * sizeof(int));
+    std::memcpy(h + o_xf, iv_xf.data(), iv_xf.size() * sizeof(DXform));
+    if (normals) std::memcpy(h + o_nrm, normals, n * 36);
+    if (tangents) std::memcpy(h + o_tan, tangents, n * 36);
+    if (uvs) std::memcpy(h + o_uv, uvs, n * 24);
+    char* dv = s->vertex_stage.as<char>();
+    HIP_TRY(hipMemcpyAsync(dv, h, total, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipEventRecord(st->ev, c->stream));
+    DSetTris A{};
+    A.first = first_tri, A.n = n_tris, A.n_iv = (int)iv_start.size();
+    A.iv_start = reinterpret_cast<const int*>(dv + o_start);
+    A.iv_xf = reinterpret_cast<const DXform*>(dv + o_xf);
+    A.in_pos = reinterpret_cast<const float*>(dv + o_pos);
+    A.in_nrm = normals ? reinterpret_cast<const float*>(dv + o_nrm) : nullptr;
+    A.in_tan = tangents ? reinterpret_cast<const float*>(dv + o_tan) : nullptr;
+    A.in_uv = uvs ? reinterpret_cast<const float*>(dv + o_uv) : nullptr;
+    A.base_pos = s->base_pos.as<float>();
+    A.base_nrm = D.normals ? s->base_nrm.as<float>() : nullptr;
+    A.base_tan = D.tangents ? s->base_tan.as<float>() : nullptr;
+    A.pos = s->positions.as<float>();
+    A.nrm = D.normals ? s->normals.as<float>() : nullptr;
+    A.tan = D.tangents ? s->tangents.as<float>() : nullptr;
+    A.uvs = D.uvs ? s->uvs.as<float>() : nullptr;
+    A.shade = D.tri_shade ? s->tri_shade.as<float>() : nullptr;
+    A.slot_of_prim = s->slot_of_prim.as<int>();
+    A.leaf = s->leaf_tris.as<float4>();
+    hk::launch_set_tris(c->stream, A);
+    HIP_TRY(hipGetLastError());
+    hk::merge_block_boxes(s->block_box, T, first_tri, n_tris, hk_scene::XF_BLOCK, fresh);
+    return refit_tree(s);
+}
+
+namespace {
+// the root node's boxes as the device holds them (the stream has been waited for)
+int root_area(hk_scene* s, double& area) {
+    DNode root;
+    HIP_TRY(hipMemcpy(&root, s->nodes.p, sizeof root, hipMemcpyDeviceToHost));
+    float lo[2][3], hi[2][3];
+    hk_unpack_node_boxes(root, lo, hi);
+    area = hk_root_area(lo, hi);
+    return HK_OK;
+}
+}  // namespace
+
+extern "C" int32_t hk_scene_bvh_cost(hk_scene* s, double* cost_now, double* cost_created) {
+    if (!s) return fail(HK_ERR_INVALID, "hk_scene_bvh_cost: null scene");
+    if (cost_created) *cost_created = s->cost_created;
+    if (!cost_now) return HK_OK;
+    *cost_now = 0.0;
+    const int N = s->bvh_nodes;
+    if (N <= 0) return HK_OK;   // the root is a leaf (or there is no triangle): no inner node, no cost
+    hk_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    KnobScope knobs(&c->knobs);
+    if (int e = join_lanes(c)) return e;
+    const int nb = hk::bvh_cost_blocks(N);
+    if (!s->cost_partial.p) HIP_TRY(s->cost_partial.alloc((size_t)nb * sizeof(double)));
+    hk::launch_bvh_cost(c->stream, s->nodes.as<DNode>(), N, s->cost_partial.as<double>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::vector<double> part((size_t)nb);
+    HIP_TRY(hipMemcpy(part.data(), s->cost_partial.p, part.size() * sizeof(double), hipMemcpyDeviceToHost));
+    double sum = 0.0, area = 0.0;
+    for (double v : part) sum += v;   // in block order
+    if (int e = root_area(s, area)) return e;
+    *cost_now = area > 0.0 ? sum / area : 0.0;
+    return HK_OK;
+}
+
+extern "C" int32_t hk_scene_bvh_copy(hk_scene* s, int32_t* n_nodes, float* boxes, int32_t* refs) {
+    if (!s || !n_nodes) return fail(HK_ERR_INVALID, "hk_scene_bvh_copy: null argument");
+    const int N = s->bvh_nodes;
+    *n_nodes = N;
+    if (N <= 0 || (!boxes && !refs)) return HK_OK;
+    hk_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    KnobScope knobs(&c->knobs);
+    if (int e = join_lanes(c)) return e;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::vector<DNode> dn((size_t)N);
+    HIP_TRY(hipMemcpy(dn.data(), s->nodes.p, dn.size() * sizeof(DNode), hipMemcpyDeviceToHost));
+    for (int i = 0; i < N; ++i) {
+        if (boxes) {
+            float lo[2][3], hi[2][3];
+            hk_unpack_node_boxes(dn[i], lo, hi);
+            for (int ch = 0; ch < 2; ++ch)
+                for (int k = 0; k < 3; ++k) boxes[12 * (size_t)i + 6 * ch + k] = lo[ch][k], boxes[12 * (size_t)i + 6 * ch + 3 + k] = hi[ch][k];
+        }
+        if (refs) refs[2 * (size_t)i] = dn[i].c0, refs[2 * (size_t)i + 1] = dn[i].c1;
+    }
     return HK_OK;
 }

@@ -218,6 +218,20 @@ struct DXform {
 struct DQGrid {
     float base[3], cell[3];
 };
+// hk_scene_set_vertices: what one k_set_tris launch reads and writes.  in_*: the uploaded arrays of triangles [first, first + n), 9 / 9 /
+// 9 / 6 floats per triangle (null: that attribute keeps its base values).  iv_start[0 .. n_iv) ascending, iv_start[0] <= first: scene
+// triangle t >= iv_start[j] (and < iv_start[j + 1]) is under transform iv_xf[j].  nrm / tan / uvs are null in a scene without them
+// (base_nrm / base_tan likewise), shade in a scene without packed records.
+struct DSetTris {
+    int first, n, n_iv;
+    const int* iv_start;
+    const DXform* iv_xf;
+    const float *in_pos, *in_nrm, *in_tan, *in_uv;
+    float *base_pos, *base_nrm, *base_tan;
+    float *pos, *nrm, *tan, *uvs, *shade;
+    const int* slot_of_prim;
+    float4* leaf;
+};
 
 struct DScene {
     const DNode* nodes;

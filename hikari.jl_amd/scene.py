@@ -190,24 +190,100 @@ class Scene:
         if moved:
             self._replace_lights(moved)
 
-    def _moved_area_lights(self, instance, m34):
-        """[(index into self.lights, DiffuseAreaLight)] of the instance's faces that carry a light, from the mesh as pushed moved by m34."""
+    def _mesh_index(self, instance):
+        """Position in self._meshes of the mesh `instance` was pushed as."""
         first = 0
-        for mesh, metas in self._meshes:
+        for k, (mesh, _) in enumerate(self._meshes):
             if first == instance.first_tri and mesh.n_faces == instance.n_tris:
-                break
+                return k
             first += mesh.n_faces
-        else:
-            raise ValueError("instance %r is not a mesh of this scene" % (instance,))
+        raise ValueError("instance %r is not a mesh of this scene" % (instance,))
+
+    def _moved_area_lights(self, instance, m34, positions=None, uvs=None):
+        """[(index into self.lights, DiffuseAreaLight)] of the instance's faces that carry a light, from the kept mesh (or `positions` /
+        `uvs` in its place) moved by m34."""
+        mesh, metas = self._meshes[self._mesh_index(instance)]
         faces = np.nonzero(metas[:, 2])[0]
-        P = _transform_points(m34, mesh.positions[faces])
+        P = _transform_points(m34, (mesh.positions if positions is None else positions)[faces])
         out = []
-        for vs, idx1 in zip(P, metas[faces, 2]):
+        for face, vs, idx1 in zip(faces, P, metas[faces, 2]):
             old = self.lights[int(idx1) - 1]
             geo = _face_light_geometry(vs)
             normal, area = geo if geo is not None else (np.asarray(old.normal, dtype=f32), 0.0)
-            out.append((int(idx1) - 1, L.DiffuseAreaLight(vs.copy(), normal, float(area), np.array(old.uv, dtype=f32), old.Le, old.scale, old.two_sided)))
+            uv = np.array(old.uv if uvs is None else uvs[face], dtype=f32)
+            out.append((int(idx1) - 1, L.DiffuseAreaLight(vs.copy(), normal, float(area), uv, old.Le, old.scale, old.two_sided)))
         return out
+
+    def set_vertices(self, instance, positions, normals=None, uvs=None, move_lights=False):
+        """New vertices for the mesh of `instance` (the SceneInstance of push_instance): positions [n_tris, 3, 3] and, optionally,
+        normals [n_tris, 3, 3] and uvs [n_tris, 3, 2] replace the kept UN-transformed mesh — device scenes created later are built
+        from it — the kept description, and, through hk_scene_set_vertices, the base geometry of every device scene already created.
+        The instance keeps its transform.  An attribute left None keeps its values.
+
+        move_lights=False (the default): area lights stay as they are, as with set_transform (Q18).  move_lights=True: every face
+        light of the instance is recomputed from the new vertices under the instance's current transform (_face_light_geometry, a
+        degenerate face keeping its record with area = 0, as set_transform(move_lights=True) does) and, with `uvs`, carries the new
+        uvs; its Le is kept (a textured emission is not sampled again).  Which faces emit does not change.
+
+        ValueError for what the library would refuse: a wrong shape, a non-finite position, normals / uvs for a mesh pushed without."""
+        if not isinstance(instance, SceneInstance):
+            raise TypeError("set_vertices takes the SceneInstance push_instance returned")
+        k = self._mesh_index(instance)
+        mesh, metas = self._meshes[k]
+        n = instance.n_tris
+
+        def take(a, shape, what):
+            a = np.asarray(a)
+            if a.shape != shape:
+                raise ValueError("set_vertices: %s must have shape %s, got %s" % (what, shape, a.shape))
+            with np.errstate(over="ignore"):
+                return np.ascontiguousarray(a, dtype=f32)
+
+        if n < 1:
+            raise ValueError("instance %r has no triangles" % (instance,))
+        P = take(positions, (n, 3, 3), "positions")
+        if not np.isfinite(P).all():
+            raise ValueError("set_vertices: positions have non-finite entries")
+        N = U = None
+        if normals is not None:
+            if mesh.normals is None:
+                raise ValueError("set_vertices: normals for a mesh pushed without normals")
+            N = take(normals, (n, 3, 3), "normals")
+        if uvs is not None:
+            if mesh.uvs is None:
+                raise ValueError("set_vertices: uvs for a mesh pushed without uvs")
+            U = take(uvs, (n, 3, 2), "uvs")
+        moved = []
+        if move_lights:
+            m34 = self._transforms.get((instance.first_tri, n), np.eye(3, 4, dtype=f32))
+            moved = self._moved_area_lights(instance, m34, P, U)
+        self._meshes[k] = (G.Mesh(P.copy(), mesh.normals if N is None else N.copy(), mesh.uvs if U is None else U.copy()), metas)
+        a, e = instance.first_tri, instance.first_tri + n
+        if self._desc is not None:              # the arrays the kept description points into, rewritten in place
+            kept_p, kept_n, kept_uv = self._keep[:3]
+            kept_p[a:e] = P
+            if N is not None:
+                kept_n[a:e] = N
+            if U is not None:
+                kept_uv[a:e] = U
+            lo, hi = kept_p.reshape(-1, 3).min(axis=0), kept_p.reshape(-1, 3).max(axis=0)
+            c = (lo + hi) * f32(0.5)
+            self.bounds = (lo, hi, c, float(np.linalg.norm(hi - c)))
+        from . import _lib
+        ptr = lambda arr: None if arr is None else arr.ctypes.data_as(A.PF)
+        for h in (getattr(self, "_device", None) or {}).values():
+            _lib.check(_lib.lib().hk_scene_set_vertices(h, a, n, ptr(P), ptr(N), None, ptr(U)), "hk_scene_set_vertices")
+        if moved:
+            self._replace_lights(moved)
+
+    def bvh_cost(self, ctx):
+        """(now, created) of hk_scene_bvh_cost for this scene on `ctx`: the cost of the BVH as the device holds it after the refits
+        of set_transform / set_vertices, and of the tree as hk_scene_create built it.  now / created is the quantity to watch when
+        deciding whether to build the scene anew (sync())."""
+        from . import _lib, volpath
+        now, created = C.c_double(), C.c_double()
+        _lib.check(_lib.lib().hk_scene_bvh_cost(volpath.scene_handle(ctx, self), C.byref(now), C.byref(created)), "hk_scene_bvh_cost")
+        return now.value, created.value
 
     # ---- lights and environment maps in place (hk_scene_update_lights, hk_scene_update_envmap) --------------------------------
     def _flat_index(self, index):

@@ -355,9 +355,10 @@ int32_t hk_scene_destroy(hk_scene* scene);
  * call (HK_ERR_INVALID, hk_last_error says why) leaves the scene untouched.
  *
  * hk_scene_set_transform: the world positions, normals and tangents of triangles [first_tri, first_tri + n_tris) become m34 (3x4
- * row-major affine) applied to the values those triangles had at hk_scene_create ("base"); the BVH keeps its topology and its boxes
- * are refit on the device (traversal slows after large moves: recreate the scene then).  Area lights and the light BVH stay as
- * created (they are built from the un-transformed mesh, Q18).  Binary32 without contraction, in this order:
+ * row-major affine) applied to the values those triangles had at hk_scene_create or were given by the last hk_scene_set_vertices
+ * ("base"); the BVH keeps its topology and its boxes are refit on the device (traversal slows as the boxes of a tree built for the old
+ * geometry grow and overlap: the quantity to watch is cost_now / cost_created of hk_scene_bvh_cost).  Area lights and the light BVH stay
+ * as created (they are built from the un-transformed mesh, Q18).  Binary32 without contraction, in this order:
  *   points    p'[k] = ((m[k][0]*x + m[k][1]*y) + m[k][2]*z) + m[k][3]
  *   normals   A = m[:, 0..2]; C[i][j] = A[i+1][j+1]*A[i+2][j+2] - A[i+1][j+2]*A[i+2][j+1] (indices mod 3) and
  *             det = (A[0][0]*C[0][0] + A[0][1]*C[0][1]) + A[0][2]*C[0][2] in double; N[i][j] = (float)(C[i][j] / det);
@@ -366,6 +367,17 @@ int32_t hk_scene_destroy(hk_scene* scene);
  *   tangents  as normals with A in place of N
  *   identity  an m34 that is exactly [I | 0] copies the base values back (the scene as created, bit for bit)
  * Refused: a null pointer, a scene without triangles, n_tris < 1 or a range outside the scene, a non-finite or singular m34.
+ *
+ * hk_scene_set_vertices: the arrays given become the new BASE geometry of triangles [first_tri, first_tri + n_tris): positions and, where
+ * given, normals and tangents (9 floats per triangle each) and uvs (6 per triangle).  A NULL normals / tangents / uvs keeps that
+ * attribute's base values for the range.  Transforms are kept: each triangle of the range is put under the transform in force on it
+ * (the last hk_scene_set_transform that covered it, the identity otherwise — a range may straddle several), by the arithmetic above,
+ * an identity as a copy; uvs are not transformed.  The triangle count, the BVH topology, materials and which triangles emit do not
+ * change; the boxes are refit as for hk_scene_set_transform, and area lights and the light BVH stay as they are (Q18).  The arrays are
+ * borrowed for the call (copied through pinned memory owned by the scene) and cross to the device once; one kernel rewrites every copy
+ * of the geometry.  A range larger than any before grows a device buffer, which waits for earlier edits of the scene — the one wait.
+ * Refused: a null scene or positions, a scene without triangles, n_tris < 1 or a range outside the scene, a non-finite position,
+ * normals / tangents / uvs for a scene created without that array (which arrays exist selects code paths and cannot change).
  *
  * hk_scene_update_materials: material records [first, first + n) of hk_scene_desc::materials are replaced by materials[0 .. n-1]
  * (upload through pinned memory owned by the scene).  Refused: a null pointer, n < 1 or a range outside the scene, and a record that
@@ -421,6 +433,9 @@ int32_t hk_scene_destroy(hk_scene* scene);
  * the first time in a scene whose only medium is grey.  The classes select kernels and size the integrator's path state.  Every refusal
  * of this call is HK_ERR_INVALID. */
 int32_t hk_scene_set_transform(hk_scene* scene, int32_t first_tri, int32_t n_tris, const float* m34);
+int32_t hk_scene_set_vertices(hk_scene* scene, int32_t first_tri, int32_t n_tris, const float* positions /* 9 per triangle */,
+                              const float* normals /* 9 per triangle or NULL */, const float* tangents /* 9 per triangle or NULL */,
+                              const float* uvs /* 6 per triangle or NULL */);
 int32_t hk_scene_update_materials(hk_scene* scene, int32_t first, int32_t n, const hk_material* materials);
 int32_t hk_scene_update_lights(hk_scene* scene, int32_t first, int32_t n, const hk_light* lights);
 int32_t hk_scene_update_envmap(hk_scene* scene, int32_t idx, const float* data, const float* rotation);
@@ -449,7 +464,7 @@ int32_t hk_film_clear(hk_film* film); /* clear!(vp), volpath.jl:108-113 */
  *     following on) are rendered as ONE pass — bit-identical film, a seventh of the time — when the note reaches HK_BATCH_PATHS_M
  *     (64 M paths), when a call comes that does not continue it, or when anything looks: hk_flush, hk_sync, every hk_film_* / hk_stats_* /
  *     hk_*_destroy / hk_ctx_set_option /
- *     hk_scene_set_transform / hk_scene_update_materials / hk_scene_update_lights / hk_scene_update_envmap / hk_scene_update_medium entry point.  hk_flush enqueues the noted calls without waiting for them.
+ *     hk_scene_set_transform / hk_scene_set_vertices / hk_scene_update_materials / hk_scene_update_lights / hk_scene_update_envmap / hk_scene_update_medium entry point.  hk_flush enqueues the noted calls without waiting for them.
  *     HK_BATCH_PATHS_M=0 (hk_ctx_set_option) turns the noting off.
  * Argument errors are reported by the call itself; a device error of a deferred pass by the call that flushes it — also by the
  * destroy entry points, which still destroy their object. */
@@ -641,6 +656,18 @@ int32_t hk_test_trace_lean(hk_ctx* ctx, hk_scene* scene, int32_t anyhit, int32_t
 int32_t hk_scene_bvh_info(hk_scene* scene, int32_t* n_nodes, int32_t* n_leaf_tris, int32_t* max_depth);
 int32_t hk_scene_light_bvh_copy(hk_scene* scene, int32_t* n_nodes, float* nodes_out /* 16 floats per node */,
                                 uint32_t* bit_trails /* n_lights */);
+/* The cost of the scene's BVH as the device holds it (cost_now) and as hk_scene_create built it (cost_created): the sum over the inner
+   nodes and both children of A(child box) * w / A(root), A = 2(dx*dy + dx*dz + dy*dz) of the float boxes in double (an empty box: 0),
+   w = 1 for an inner child and the triangle count for a leaf child, the root box the union of the root node's two child boxes.  Refits
+   (hk_scene_set_transform, hk_scene_set_vertices) keep the topology, so cost_now / cost_created says how much more box area a ray meets
+   than in a tree built for the geometry: the quantity to watch when deciding to create the scene anew.  cost_now is reduced on the
+   device without atomics (the same tree gives the same bits) and waits for the context's stream; either pointer may be NULL.  Both are 0
+   for a scene without inner nodes. */
+int32_t hk_scene_bvh_cost(hk_scene* scene, double* cost_now, double* cost_created);
+/* The float nodes as the device holds them: n_nodes inner nodes, breadth-first, node 0 the root; boxes = the two child boxes of every
+   node (lo0[3] hi0[3] lo1[3] hi1[3]), refs = the two child references (>= 0: an inner node; < 0: ~ref = first leaf slot << 3 | count - 1).
+   Waits for the context's stream.  Either array may be NULL. */
+int32_t hk_scene_bvh_copy(hk_scene* scene, int32_t* n_nodes, float* boxes /* 12 per node: lo0 hi0 lo1 hi1 */, int32_t* refs /* 2 per node */);
 
 /* The majorant grid (n_cells floats, index x + rx*(y + ry*z)) and the zero-cell mask ((n_cells + 31) / 32 words, bit c of the mask = cell c)
    of medium `idx` as the device holds them; waits for the context's stream.  Either array may be NULL; n_cells = 0 for a homogeneous medium. */

@@ -714,6 +714,50 @@ function update_medium!(vp::MI355XVolPath, index::Integer, medium)
     nothing
 end
 
+"""
+    set_vertices!(vp, first_tri, positions; normals = nothing, uvs = nothing)
+
+New base geometry for triangles `first_tri` (0-based, in the order `flatten_scene` uploads them) onwards of the scene on the devices:
+`positions` is a `3 x 3 x n` `Float32` array (coordinate, vertex, triangle — 9 floats per triangle in memory), `normals` likewise and `uvs`
+`2 x 3 x n`, or `nothing` to keep what the triangles have.  The transform of the range is kept and the BVH is refit on the device; the
+triangle count cannot change.  `bvh_cost` says when the refit tree has become slow.
+"""
+function set_vertices!(vp::MI355XVolPath, first_tri::Integer, positions; normals = nothing, uvs = nothing)
+    P = Array{Float32}(positions)
+    N = normals === nothing ? nothing : Array{Float32}(normals)
+    U = uvs === nothing ? nothing : Array{Float32}(uvs)
+    length(P) % 9 == 0 || error("HikariMI355X: set_vertices! takes 9 floats per triangle")
+    n = length(P) ÷ 9
+    (N === nothing || length(N) == 9n) && (U === nothing || length(U) == 6n) || error("HikariMI355X: set_vertices!: normals / uvs do not match the positions")
+    GC.@preserve P N U begin
+        pn = N === nothing ? Ptr{Float32}(C_NULL) : pointer(N)
+        pu = U === nothing ? Ptr{Float32}(C_NULL) : pointer(U)
+        for d in vp.devs
+            d.scene == C_NULL && continue
+            check(ccall((:hk_scene_set_vertices, LIB), Int32, (Ptr{Cvoid}, Int32, Int32, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}), d.scene, Int32(first_tri), Int32(n),
+                        pointer(P), pn, Ptr{Float32}(C_NULL), pu), "hk_scene_set_vertices")
+        end
+    end
+    nothing
+end
+
+"""
+    bvh_cost(vp) -> (now, created)
+
+The cost of the scene's BVH on the first device as it stands after refits, and as it was built; `now / created` is the quantity to watch
+when deciding whether to flatten and create the scene anew.
+"""
+function bvh_cost(vp::MI355XVolPath)
+    now = Ref{Float64}(0.0)
+    created = Ref{Float64}(0.0)
+    for d in vp.devs
+        d.scene == C_NULL && continue
+        check(ccall((:hk_scene_bvh_cost, LIB), Int32, (Ptr{Cvoid}, Ref{Float64}, Ref{Float64}), d.scene, now, created), "hk_scene_bvh_cost")
+        break
+    end
+    (now[], created[])
+end
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # postprocess! / denoise! / fill_aux_buffers! forwards (postprocess.jl:293-357, denoise.jl:301-376, film.jl:410-483)
 # ---------------------------------------------------------------------------------------------------------------------------
