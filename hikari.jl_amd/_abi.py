@@ -143,6 +143,7 @@ EXPORTED_SYMBOLS = [
     "hk_film_pin_host", "hk_film_unpin_host", "hk_scene_set_transform", "hk_scene_update_materials", "hk_scene_update_lights", "hk_scene_update_envmap",
     "hk_film_update_aux", "hk_film_read_aux", "hk_film_present", "hk_film_present_async",
     "hk_scene_update_medium", "hk_scene_medium_copy", "hk_test_medium_bricks", "hk_scene_set_vertices", "hk_scene_bvh_cost", "hk_scene_bvh_copy",
+    "hk_scene_bvh_leaves", "hk_scene_rebuild_bvh",
 ]
 
 # prototypes (argtypes, restype) of the geometry edit and the tree introspection, in the header's order; _lib.py installs them
@@ -151,4 +152,6 @@ PROTOTYPES = {
     "hk_scene_set_vertices": ([_VP, _I32, _I32, PF, PF, PF, PF], _I32),
     "hk_scene_bvh_cost": ([_VP, _PD, _PD], _I32),
     "hk_scene_bvh_copy": ([_VP, _PI32, PF, _PI32], _I32),
+    "hk_scene_bvh_leaves": ([_VP, _PI32, _PI32], _I32),
+    "hk_scene_rebuild_bvh": ([_VP], _I32),
 }

@@ -3,9 +3,11 @@
 // Replaces what the reference gets from Raycore's TLAS/BVH (src/scene.jl:120-149 `sync!`, call sites
 // src/integrators/volpath/intersection.jl:200,225,323,703).  Binned SAH (32 bins; 16 until round 5), leaves of <= 4
 // triangles, depth bounded so a per-lane stack of HK_LDS_STACK entries can never overflow: a split
-// is only taken if both children can still be finished by median splits inside the depth budget.
+// is only taken if both children can still be finished by median splits inside the depth budget.  The per-node decision (bin index,
+// sweep, empty-side rule, depth budget) is hk_bvh_decide.h's, shared with the device builder of hk_scene_rebuild_bvh.
 // Output layout: DNode (64 B, both child boxes inline) + leaf-ordered 48-B triangles.
 #include "bvh_build.h"
+#include "hk_bvh_decide.h"
 
 #include <algorithm>
 #include <cmath>
@@ -43,12 +45,6 @@ struct Box {
     }
 };
 
-int ceil_log2(int v) {
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return l;
-}
-
 struct Builder {
     const float* pos;
     std::vector<Box> tb;
@@ -57,9 +53,7 @@ struct Builder {
     BVH& out;
     int max_depth_seen = 0;
     int LEAF = 4;
-    static constexpr int MAXBINS = 64;
     int NBINS = 16;
-    static constexpr int DEPTH_BUDGET = 30;  // < HK_LDS_STACK
 
     Builder(const float* p, int n, BVH& o) : pos(p), out(o) {
         tb.resize(n);
@@ -72,9 +66,6 @@ struct Builder {
             idx[i] = i;
         }
     }
-    // levels a median-split subtree with `count` triangles still needs (leaf capacity LEAF)
-    int levels_needed(int count) const { return count <= LEAF ? 0 : ceil_log2((count + LEAF - 1) / LEAF); }
-
     int make_leaf(int first, int count) {
         int start = (int)out.leaf_prims.size();
         for (int i = 0; i < count; ++i) out.leaf_prims.push_back(idx[first + i]);
@@ -91,62 +82,38 @@ struct Builder {
         }
         max_depth_seen = std::max(max_depth_seen, depth);
         if (count <= LEAF) return make_leaf(first, count);
-        // binned SAH
-        int best_axis = -1, best_split = -1;
-        float best_cost = std::numeric_limits<float>::infinity();
+        // binned SAH: the bins of every axis with extent, then the decision both builders share (hk_bvh_decide.h)
+        HkBvhBins bins[3];
         for (int axis = 0; axis < 3; ++axis) {
             float ext = cb.hi[axis] - cb.lo[axis];
             if (!(ext > 0)) continue;
-            Box bins[MAXBINS];
-            int cnt[MAXBINS] = {0};
-            for (auto& b : bins) b.reset();
-            float scale = NBINS / ext;
+            HkBvhBins& B = bins[axis];
+            for (int b = 0; b < NBINS; ++b) {
+                for (int k = 0; k < 3; ++k) B.lo[b][k] = std::numeric_limits<float>::infinity(), B.hi[b][k] = -std::numeric_limits<float>::infinity();
+                B.cnt[b] = 0;
+            }
+            float scale = hk_bvh_bin_scale(ext, NBINS);
             for (int i = first; i < first + count; ++i) {
-                int b = (int)((cent[3 * (size_t)idx[i] + axis] - cb.lo[axis]) * scale);
-                b = std::min(std::max(b, 0), NBINS - 1);
-                bins[b].grow(tb[idx[i]]);
-                cnt[b]++;
-            }
-            float right_area[MAXBINS];
-            int right_cnt[MAXBINS];
-            Box acc;
-            acc.reset();
-            int c = 0;
-            for (int b = NBINS - 1; b >= 1; --b) {
-                acc.grow(bins[b]);
-                c += cnt[b];
-                right_area[b] = acc.half_area();
-                right_cnt[b] = c;
-            }
-            acc.reset();
-            c = 0;
-            for (int b = 0; b < NBINS - 1; ++b) {
-                acc.grow(bins[b]);
-                c += cnt[b];
-                if (c == 0 || right_cnt[b + 1] == 0) continue;
-                float cost = acc.half_area() * (float)c + right_area[b + 1] * (float)right_cnt[b + 1];
-                if (cost < best_cost) {
-                    best_cost = cost;
-                    best_axis = axis;
-                    best_split = b;
-                }
+                int b = hk_bvh_bin_of(cent[3 * (size_t)idx[i] + axis], cb.lo[axis], scale, NBINS);
+                hk_bvh_grow(B.lo[b], B.hi[b], tb[idx[i]].lo, tb[idx[i]].hi);
+                B.cnt[b]++;
             }
         }
+        const HkBvhSplit sp = hk_bvh_decide(cb.lo, cb.hi, bins, count, depth, LEAF, NBINS);
         int mid = -1;
-        if (best_axis >= 0) {
+        if (sp.axis >= 0) {
+            const int best_axis = sp.axis, best_split = sp.split;
             float ext = cb.hi[best_axis] - cb.lo[best_axis];
-            float scale = NBINS / ext;
+            float scale = hk_bvh_bin_scale(ext, NBINS);
             auto it = std::partition(idx.begin() + first, idx.begin() + first + count, [&](int t) {
-                int b = (int)((cent[3 * (size_t)t + best_axis] - cb.lo[best_axis]) * scale);
-                b = std::min(std::max(b, 0), NBINS - 1);
-                return b <= best_split;
+                return hk_bvh_bin_of(cent[3 * (size_t)t + best_axis], cb.lo[best_axis], scale, NBINS) <= best_split;
             });
             mid = (int)(it - idx.begin());
-            int nl = mid - first, nr = count - nl;
-            // depth budget: both sides must still fit with median splits
-            if (nl == 0 || nr == 0 || depth + 1 + levels_needed(std::max(nl, nr)) > DEPTH_BUDGET) mid = -1;
+            // depth budget: both sides must still fit with median splits (decided from the bin counts: the partition's sizes)
+            if (sp.median) mid = -1;
         }
         if (mid < 0) {
+            ++out.median_splits;
             int axis = 0;
             float e = cb.hi[0] - cb.lo[0];
             for (int k = 1; k < 3; ++k)
@@ -181,11 +148,12 @@ void build_bvh(const float* positions, int n_tris, BVH& out, int leaf_size, int 
     out.nodes.clear();
     out.leaf_prims.clear();
     out.max_depth = 0;
+    out.median_splits = 0;
     out.root_ref = ~0;  // empty leaf marker handled by n_tris == 0
     if (n_tris <= 0) return;
     Builder b(positions, n_tris, out);
-    b.LEAF = leaf_size >= 1 && leaf_size <= 8 ? leaf_size : 4;
-    b.NBINS = std::min(std::max(bins, 4), (int)Builder::MAXBINS);   // (HK_BVH_BINS)   // (HK_BVH_LEAF, resolved by the caller from its context's knobs)
+    b.LEAF = hk_bvh_leaf_size(leaf_size);   // (HK_BVH_LEAF, resolved by the caller from its context's knobs)
+    b.NBINS = hk_bvh_bin_count(bins);       // (HK_BVH_BINS)
     Box box;
     out.root_ref = b.build(0, n_tris, 0, box);
     out.max_depth = b.max_depth_seen;

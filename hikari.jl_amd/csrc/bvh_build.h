@@ -17,7 +17,9 @@ struct BVH {
     int root_ref = 0;
     int max_depth = 0;
     float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    int median_splits = 0;        // nodes cut at count / 2 instead of a SAH boundary (coincident centroids, or the depth budget)
 };
+#define HK_BVH_COUNTS_MEDIANS 1
 void build_bvh(const float* positions, int n_tris, BVH& out, int leaf_size = 4, int bins = 32);   // leaf_size: triangles per leaf, 1 .. 8; bins: SAH bins per axis, 4 .. 64
 // (32 bins since round 5: the 10^6-triangle scene's traversal - 1.7 %, its any-hit casts - 1.5 % against 16, 64 no better, 8 + 1 %; the small scenes unchanged)
 

@@ -264,6 +264,8 @@ struct hk_scene {
     DevBuf vertex_stage;                    // hk_scene_set_vertices: the uploaded range and its interval table, read by k_set_tris (grows with the largest range)
     DevBuf cost_partial;                    // hk_scene_bvh_cost: the per-block sums of k_bvh_cost (first call)
     double cost_created = 0.0;              // the tree cost of the tree as built (hk_scene_bvh_cost)
+    DevBuf rebuilt_cost;                    // hk_scene_rebuild_bvh: k_bvh_cost's sums over the tree it built, then that tree's root node
+    int rebuilt_cost_blocks = 0;            // > 0: rebuilt_cost holds that many sums the host has not yet made cost_created of
     bool have_base = false;
     bool qnodes_built = false;              // s->qnodes holds a quantised tree (D.qnodes is null while no grid is known to contain it)
     enum { XF_BLOCK = 1024 };

@@ -55,6 +55,10 @@ void launch_set_tris(hipStream_t s, const DSetTris& A);
 // hk_scene_bvh_cost: partial[b] = the cost terms of nodes [256 b, 256 b + 256) (bvh_cost_blocks(n) of them)
 inline int bvh_cost_blocks(int n_nodes) { return (n_nodes + 255) / 256; }
 void launch_bvh_cost(hipStream_t s, const DNode* nodes, int n, double* partial);
+// hk_scene_rebuild_bvh: the topology of a new tree over B.pos into B.nodes / B.qnodes / B.order / B.ctl (boxes: launch_refit_level
+// afterwards), then the leaf records of that order
+void launch_bvh_build(hipStream_t s, const DBuild& B);
+void launch_bvh_build_leaves(hipStream_t s, const DBuildLeaves& A);
 void launch_envmap_tables(hipStream_t s, const DEnvMap& e, DEnvMap* record);
 // hk_scene_update_medium: majorant grid + zero-cell mask of a Grid / RGB grid / NanoVDB medium, and the NanoVDB halo bricks, from the data `m` points to
 void launch_majorant_grid(hipStream_t s, const DMedium& m);

@@ -424,6 +424,21 @@ void launch_set_tris(hipStream_t s, const DSetTris& A) { hipLaunchKernelGGL(k_se
 void launch_bvh_cost(hipStream_t s, const DNode* nodes, int n, double* partial) {
     hipLaunchKernelGGL(k_bvh_cost, dim3((unsigned)bvh_cost_blocks(n)), dim3(256), 0, s, nodes, n, partial);
 }
+// hk_scene_rebuild_bvh: every launch of the device builder (k_build_*), top level first; nothing is read back in between
+void launch_bvh_build(hipStream_t s, const DBuild& B) {
+    const int T = B.n_tris;
+    hipLaunchKernelGGL(k_build_init, dim3(grid_for(T, 256, 8192)), dim3(256), 0, s, B);
+    const int position_blocks = grid_for(T, 256, 2048), segment_blocks = std::min(T / (B.leaf + 1) + 1, 4096);
+    for (int L = 0; L < HK_BUILD_MAX_LEVELS; ++L) {
+        if (B.large_cap > 0) {
+            hipLaunchKernelGGL(k_build_large_bounds, dim3(position_blocks), dim3(256), 0, s, B, L);
+            hipLaunchKernelGGL(k_build_large_bins, dim3(position_blocks), dim3(256), 0, s, B, L);
+        }
+        hipLaunchKernelGGL(k_build_split, dim3(segment_blocks), dim3(256), 0, s, B, L);
+        hipLaunchKernelGGL(k_build_emit, dim3(1), dim3(1024), 0, s, B, L);
+    }
+}
+void launch_bvh_build_leaves(hipStream_t s, const DBuildLeaves& A) { hipLaunchKernelGGL(k_build_leaves, dim3(grid_for(A.n_tris, 256, 8192)), dim3(256), 0, s, A); }
 // the Distribution2D tables of map `e` (a host copy of the record: sizes and table pointers) from its texels; `record` is the device record
 void launch_envmap_tables(hipStream_t s, const DEnvMap& e, DEnvMap* record) {
     hipLaunchKernelGGL(k_envmap_rows, dim3((e.nv + 63) / 64), dim3(64), 0, s, e.data, e.nu, e.nv, const_cast<float*>(e.cond_func), const_cast<float*>(e.cond_cdf),

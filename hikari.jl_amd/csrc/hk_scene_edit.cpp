@@ -1,12 +1,16 @@
 // hk_scene_edit.cpp — in-place scene edits: hk_scene_set_transform (device transform + BVH refit), hk_scene_set_vertices (new base
 // geometry of a triangle range in one device pass + BVH refit), hk_scene_update_materials, hk_scene_update_lights (records + host
 // rebuild of the light BVH), hk_scene_update_envmap (rotation, texels + device table build) and hk_scene_update_medium (record, volume
-// data + device build of majorant grid, zero-cell mask and NanoVDB bricks); hk_scene_bvh_cost / hk_scene_bvh_copy read the refit tree back.
+// data + device build of majorant grid, zero-cell mask and NanoVDB bricks) and hk_scene_rebuild_bvh (a new BVH topology built on the
+// device); hk_scene_bvh_cost / hk_scene_bvh_copy / hk_scene_bvh_leaves read the tree back.
 #include "hk_host.h"
+#include "hk_bvh_decide.h"
 
 // ---- in-place scene edits -----------------------------------------------------------------------------------------------------
-// No entry point waits for the device: the noted calls are rendered first (against the scene as it was), the lanes are joined, and
-// the work is enqueued on the context's stream behind everything already there.  Every argument is checked before anything changes.
+// No entry point but hk_scene_rebuild_bvh waits for the device: the noted calls are rendered first (against the scene as it was), the
+// lanes are joined, and the work is enqueued on the context's stream behind everything already there.  Every argument is checked
+// before anything changes.  (hk_scene_rebuild_bvh waits once, for the size of the tree it built; it is also the one edit that changes
+// bvh_depth and n_nodes — what follows from that is argued at its entry point.)
 // Caches keyed by the scene that an edit must not invalidate, and why it does not: DScene::all_opaque and the HK_TRI_OPAQUE bits (opacity
 // class of every material and the medium interfaces are unchanged), kinds_mask (kinds unchanged), simple_lights / has_escape_lights
 // (lights and textures unchanged), bvh_depth and n_nodes (topology unchanged), the light BVH (built from the base geometry, Q18),
@@ -110,8 +114,14 @@ int ensure_base(hk_scene* s) {
 }
 // every box of the unchanged topology from D.positions, deepest level first; the quantised copy on a grid that holds the edited tree,
 // or the float nodes when none is known to
+int refit_levels(hk_ctx* c, const std::vector<int>& level_start, DNode* nodes, DQNode* qn, const DQGrid& grid, const float4* leaf, const float* pos) {
+    for (int L = (int)level_start.size() - 2; L >= 0; --L) {   // nothing to do when the root is a leaf
+        hk::launch_refit_level(c->stream, level_start[L], level_start[L + 1], nodes, qn, grid, leaf, pos);
+        HIP_TRY(hipGetLastError());
+    }
+    return HK_OK;
+}
 int refit_tree(hk_scene* s) {
-    hk_ctx* c = s->ctx;
     DScene& D = s->d;
     DQGrid grid{};
     DQNode* qn = nullptr;
@@ -122,11 +132,7 @@ int refit_tree(hk_scene* s) {
         }
         D.qnodes = qn;   // null: no grid is known to hold the moved tree, the traversal reads the float nodes (same hits)
     }
-    for (int L = (int)s->level_start.size() - 2; L >= 0; --L) {   // nothing to do when the root is a leaf
-        hk::launch_refit_level(c->stream, s->level_start[L], s->level_start[L + 1], s->nodes.as<DNode>(), qn, grid, D.leaf_tris, D.positions);
-        HIP_TRY(hipGetLastError());
-    }
-    return HK_OK;
+    return refit_levels(s->ctx, s->level_start, s->nodes.as<DNode>(), qn, grid, D.leaf_tris, D.positions);
 }
 }  // namespace
 
@@ -556,21 +562,45 @@ int root_area(hk_scene* s, double& area) {
     area = hk_root_area(lo, hi);
     return HK_OK;
 }
+// the cost of the tree hk_scene_rebuild_bvh built: its k_bvh_cost sums and its root node were left in rebuilt_cost on the stream (the
+// stream has been waited for)
+int take_rebuilt_cost(hk_scene* s) {
+    const int nb = s->rebuilt_cost_blocks;
+    std::vector<double> part((size_t)nb);
+    DNode root;
+    HIP_TRY(hipMemcpy(part.data(), s->rebuilt_cost.p, part.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&root, s->rebuilt_cost.as<char>() + part.size() * sizeof(double), sizeof root, hipMemcpyDeviceToHost));
+    double sum = 0.0;
+    for (double v : part) sum += v;   // in block order, as hk_scene_bvh_cost adds them
+    float lo[2][3], hi[2][3];
+    hk_unpack_node_boxes(root, lo, hi);
+    const double area = hk_root_area(lo, hi);
+    s->cost_created = area > 0.0 ? sum / area : 0.0;
+    s->rebuilt_cost_blocks = 0;
+    return HK_OK;
+}
 }  // namespace
 
 extern "C" int32_t hk_scene_bvh_cost(hk_scene* s, double* cost_now, double* cost_created) {
     if (!s) return fail(HK_ERR_INVALID, "hk_scene_bvh_cost: null scene");
+    const int N = s->bvh_nodes;
+    hk_ctx* c = s->ctx;
+    if (s->rebuilt_cost_blocks > 0) {   // a rebuild since the last call: the cost of its tree is on the device
+        HIP_TRY(hipSetDevice(c->device));
+        KnobScope knobs(&c->knobs);
+        if (int e = join_lanes(c)) return e;
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (int e = take_rebuilt_cost(s)) return e;
+    }
     if (cost_created) *cost_created = s->cost_created;
     if (!cost_now) return HK_OK;
     *cost_now = 0.0;
-    const int N = s->bvh_nodes;
     if (N <= 0) return HK_OK;   // the root is a leaf (or there is no triangle): no inner node, no cost
-    hk_ctx* c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
     KnobScope knobs(&c->knobs);
     if (int e = join_lanes(c)) return e;
     const int nb = hk::bvh_cost_blocks(N);
-    if (!s->cost_partial.p) HIP_TRY(s->cost_partial.alloc((size_t)nb * sizeof(double)));
+    if (s->cost_partial.bytes < (size_t)nb * sizeof(double)) HIP_TRY(s->cost_partial.alloc((size_t)nb * sizeof(double)));   // (first call, or a rebuilt tree with more nodes)
     hk::launch_bvh_cost(c->stream, s->nodes.as<DNode>(), N, s->cost_partial.as<double>());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -603,6 +633,129 @@ extern "C" int32_t hk_scene_bvh_copy(hk_scene* s, int32_t* n_nodes, float* boxes
                 for (int k = 0; k < 3; ++k) boxes[12 * (size_t)i + 6 * ch + k] = lo[ch][k], boxes[12 * (size_t)i + 6 * ch + 3 + k] = hi[ch][k];
         }
         if (refs) refs[2 * (size_t)i] = dn[i].c0, refs[2 * (size_t)i + 1] = dn[i].c1;
+    }
+    return HK_OK;
+}
+
+extern "C" int32_t hk_scene_bvh_leaves(hk_scene* s, int32_t* n, int32_t* prims) {
+    if (!s || !n) return fail(HK_ERR_INVALID, "hk_scene_bvh_leaves: null argument");
+    const int T = s->bvh_leaf_tris;
+    *n = T;
+    if (T <= 0 || !prims) return HK_OK;
+    hk_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    KnobScope knobs(&c->knobs);
+    if (int e = join_lanes(c)) return e;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::vector<float4> lt(3 * (size_t)T);
+    HIP_TRY(hipMemcpy(lt.data(), s->leaf_tris.p, lt.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    for (int i = 0; i < T; ++i) std::memcpy(&prims[i], &lt[3 * (size_t)i].w, 4);
+    return HK_OK;
+}
+
+// A new tree over D.positions.  What this changes, and what follows from it: nodes, quantised nodes, leaf records and the slot table
+// get new buffers (built on the stream, boxes and cost included, and exchanged at the end, after the last call that can fail: an error return leaves the scene as it was);
+// bvh_nodes / D.n_nodes, bvh_depth / D.bvh_depth and level_start follow the new tree.  Who reads the depth, and why nothing else has
+// to be invalidated: the path state's shape (pass_traits / ensure_state, hk_render.cpp: `small_scene`, grey_compact_ok) and the shadow
+// stream (`want_overlap`) are decided per render call from the DScene of that call, and ensure_state lays the state out anew — dropping
+// its view key, as for any reallocation — when the segment count it wants differs from the one it has; the view key itself holds the
+// layout (n_waves, wave_cap, compact, dynamic_segments) and the camera records do not depend on the scene, so a rebuild that keeps the
+// layout keeps the cached view.  The kernel instantiations (lean_dispatch, launch_shadow_walk, small_pass_class: hk_launch_impl.h) are
+// chosen per launch from DScene::bvh_depth, passed by value.  A scene created shallow has no block_box and no quantised copy: grown past
+// 16 levels it runs the deep instantiations on its float nodes (D.qnodes == nullptr: same hits).  A deep scene grown shallow keeps its
+// quantised copy up to date (refit_tree) and the 16-entry instantiations do not read it.  Opacity bits and prim words travel with the
+// triangles (k_build_leaves copies them from the old slot); transforms (hk_scene::xf), block_box and the base copies are indexed by
+// triangle, not by slot, and stay.
+extern "C" int32_t hk_scene_rebuild_bvh(hk_scene* s) {
+    if (!s) return fail(HK_ERR_INVALID, "hk_scene_rebuild_bvh: null scene");
+    hk_ctx* c = s->ctx;
+    DScene& D = s->d;
+    const int T = D.n_tris;
+    KnobScope knobs(&c->knobs);
+    const int leaf = hk_bvh_leaf_size(hk::knob_int("HK_BVH_LEAF", 4)), nbins = hk_bvh_bin_count(hk::knob_int("HK_BVH_BINS", 32));
+    if (s->bvh_nodes <= 0 || T <= leaf) return HK_OK;   // the root is a leaf (or would be one under the leaf size of now): nothing to build
+    HIP_TRY(hipSetDevice(c->device));
+    const int small_max = hk::knob_int_in("HK_BVH_BUILD_SMALL", 0, INT_MAX, 1024);
+    const int large_cap = (int)((long long)T / ((long long)std::max(small_max, leaf) + 1)) + 1;   // large segments are disjoint and hold more than small_max triangles each
+    const size_t n = (size_t)T, cap_nodes = (size_t)std::max(T - 1, 1);
+    const size_t cap_seg = n / ((size_t)leaf + 1) + 1;   // a level's inner nodes are disjoint and hold more than `leaf` triangles each
+    DevBuf nodes, qnodes, leaf_tris, slots, old_slots, tbox, idx, seg, large, large_cb, large_bins, n_left, order, ctl, cost;
+    HIP_TRY(nodes.alloc(cap_nodes * sizeof(DNode)));
+    if (s->qnodes_built) HIP_TRY(qnodes.alloc(cap_nodes * sizeof(DQNode)));
+    HIP_TRY(leaf_tris.alloc(3 * n * sizeof(float4)));
+    if (s->have_base) HIP_TRY(slots.alloc(n * 4));
+    else HIP_TRY(old_slots.alloc(n * 4));
+    HIP_TRY(tbox.alloc(n * 24));
+    HIP_TRY(idx.alloc(2 * n * 4));
+    HIP_TRY(seg.alloc(2 * cap_seg * sizeof(DBuildSeg)));
+    HIP_TRY(large.alloc(2 * (size_t)large_cap * 4));
+    HIP_TRY(large_cb.alloc((size_t)large_cap * 6 * 4));
+    HIP_TRY(large_bins.alloc((size_t)large_cap * HK_BUILD_BIN_WORDS * 4));
+    HIP_TRY(n_left.alloc(cap_seg * 4));
+    HIP_TRY(order.alloc(n * 4));
+    HIP_TRY(ctl.alloc(sizeof(DBuildCtl)));
+    const int cost_blocks = hk::bvh_cost_blocks((int)cap_nodes);
+    HIP_TRY(cost.alloc((size_t)cost_blocks * sizeof(double) + sizeof(DNode)));
+    if (int e = join_lanes(c)) return e;   // noted calls render the tree as it was; the lanes finish before the stream builds beside it
+    DBuild B{};
+    B.n_tris = T, B.leaf = leaf, B.nbins = nbins, B.small_max = small_max, B.large_cap = large_cap;
+    B.pos = D.positions;
+    B.tbox = tbox.as<float>();
+    B.idx[0] = idx.as<int>(), B.idx[1] = idx.as<int>() + n;
+    B.seg[0] = seg.as<DBuildSeg>(), B.seg[1] = seg.as<DBuildSeg>() + cap_seg;
+    B.large[0] = large.as<int>(), B.large[1] = large.as<int>() + large_cap;
+    B.large_cb = large_cb.as<int>(), B.large_bins = large_bins.as<int>();
+    B.n_left = n_left.as<int>(), B.order = order.as<int>();
+    B.nodes = nodes.as<DNode>();
+    B.qnodes = s->qnodes_built ? qnodes.as<DQNode>() : nullptr;
+    B.ctl = ctl.as<DBuildCtl>();
+    hk::launch_bvh_build(c->stream, B);
+    HIP_TRY(hipGetLastError());
+    DBuildLeaves A{};
+    A.n_tris = T, A.order = B.order, A.pos = D.positions, A.old_leaf = D.leaf_tris, A.leaf = leaf_tris.as<float4>();
+    if (s->have_base) A.old_slot_of_prim = s->slot_of_prim.as<int>(), A.slot_of_prim = slots.as<int>();
+    else {
+        hk::launch_slot_of_prim(c->stream, D.leaf_tris, T, old_slots.as<int>());
+        A.old_slot_of_prim = old_slots.as<int>(), A.slot_of_prim = nullptr;
+    }
+    hk::launch_bvh_build_leaves(c->stream, A);
+    HIP_TRY(hipGetLastError());
+    // the one wait: node count, depth and level table of the tree just built
+    DBuildCtl h{};
+    HIP_TRY(hipMemcpyAsync(&h, ctl.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    bool sane = h.depth >= 1 && h.depth <= HK_BVH_DEPTH_BUDGET && h.n_nodes >= 1 && (size_t)h.n_nodes <= cap_nodes && h.level_start[0] == 0 && h.level_start[h.depth] == h.n_nodes;
+    for (int L = 0; sane && L < h.depth; ++L) sane = h.level_start[L + 1] > h.level_start[L];
+    if (!sane) return fail(HK_ERR_DEVICE, "hk_scene_rebuild_bvh: the device builder reported an inconsistent tree (the scene is unchanged)");
+    // boxes of the new tree (the quantised copy on a proved grid, or none) and its cost, still into the new buffers: every launch that
+    // can be refused has been accepted before anything of the scene changes
+    const std::vector<int> levels(h.level_start, h.level_start + h.depth + 1);
+    DQGrid grid{};
+    DQNode* qn = nullptr;
+    if (s->qnodes_built && quant_grid(s, grid)) qn = qnodes.as<DQNode>();
+    if (int e = refit_levels(c, levels, nodes.as<DNode>(), qn, grid, leaf_tris.as<float4>(), D.positions)) return e;
+    // the cost of this tree (the new cost_created) stays on the device until somebody asks: no second wait here
+    const int blocks = hk::bvh_cost_blocks(h.n_nodes);
+    hk::launch_bvh_cost(c->stream, nodes.as<DNode>(), h.n_nodes, cost.as<double>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(cost.as<char>() + (size_t)blocks * sizeof(double), nodes.p, sizeof(DNode), hipMemcpyDeviceToDevice, c->stream));
+    // the exchange: nothing below can fail (the old buffers go when this function returns: the stream was waited for before the
+    // refit was enqueued, and nothing enqueued since reads them)
+    swap_buffers(s->nodes, nodes);
+    if (s->qnodes_built) swap_buffers(s->qnodes, qnodes);
+    swap_buffers(s->leaf_tris, leaf_tris);
+    if (s->have_base) swap_buffers(s->slot_of_prim, slots);
+    swap_buffers(s->rebuilt_cost, cost);
+    s->rebuilt_cost_blocks = blocks;
+    s->bvh_nodes = h.n_nodes, s->bvh_depth = h.depth;
+    s->level_start = levels;
+    D.nodes = s->nodes.as<DNode>();
+    D.leaf_tris = s->leaf_tris.as<float4>();
+    D.n_nodes = h.n_nodes, D.bvh_depth = h.depth;
+    if (s->qnodes_built) {   // as refit_tree leaves them: the copy on its grid, or null (the float nodes are read: same hits)
+        if (qn)
+            for (int k = 0; k < 3; ++k) D.q_base[k] = grid.base[k], D.q_cell[k] = grid.cell[k];
+        D.qnodes = qn ? s->qnodes.as<DQNode>() : nullptr;
     }
     return HK_OK;
 }

@@ -233,6 +233,46 @@ struct DSetTris {
     float4* leaf;
 };
 
+// hk_scene_rebuild_bvh: the device builder's state (k_build_*, hk_kernels.hip).  A SEGMENT is a range of the index array that becomes
+// an inner node: level L's segments, in breadth-first order, are nodes level_start[L] + 0, 1, ...; `large` >= 0 names the segment's
+// slot in the global bin storage (it is binned by many blocks), < 0: one block bins it in LDS.
+#define HK_BUILD_MAX_LEVELS 31   // = HK_BVH_MAX_LEVELS (hk_bvh_decide.h)
+#define HK_BUILD_BIN_WORDS (3 * 64 * 7)   // per large segment: axis, bin, (lo[3] hi[3] as ordered integers, count)
+struct DBuildSeg {
+    int first, count, large, pad;
+};
+struct DBuildCtl {   // the one block the host reads back after the build
+    int n_seg[HK_BUILD_MAX_LEVELS + 1];         // inner nodes of level L
+    int n_large[HK_BUILD_MAX_LEVELS + 1];       // ... of them binned in global memory
+    int level_start[HK_BUILD_MAX_LEVELS + 2];
+    int n_nodes, depth;
+};
+struct DBuild {
+    int n_tris, leaf, nbins, small_max, large_cap;
+    const float* pos;          // world positions, 9 floats per triangle
+    float* tbox;               // lo[3] hi[3] per triangle
+    int* idx[2];               // the triangle order, ping-pong by level
+    DBuildSeg* seg[2];         // the segments of a level, ping-pong
+    int* large[2];             // the large segments of a level: indices into seg[], ascending (so ascending in `first`)
+    int* large_cb;             // [large_cap][6] centroid box, ordered integers
+    int* large_bins;           // [large_cap][HK_BUILD_BIN_WORDS]
+    int* n_left;               // per segment of the level: triangles that went left
+    int* order;                // the final leaf order: triangle of every leaf slot
+    DNode* nodes;
+    DQNode* qnodes;            // null: the scene has no quantised copy
+    DBuildCtl* ctl;
+};
+// ... and what k_build_leaves needs to write the new leaf records: prim and flag words come from the old slot of the triangle
+struct DBuildLeaves {
+    int n_tris;
+    const int* order;
+    const float* pos;
+    const float4* old_leaf;
+    const int* old_slot_of_prim;
+    float4* leaf;
+    int* slot_of_prim;         // null: the scene keeps no slot table yet
+};
+
 struct DScene {
     const DNode* nodes;
     const DQNode* qnodes;       // null unless the tree is deeper than 16 levels (and HK_QNODES != 0)

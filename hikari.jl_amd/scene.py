@@ -285,6 +285,42 @@ class Scene:
         _lib.check(_lib.lib().hk_scene_bvh_cost(volpath.scene_handle(ctx, self), C.byref(now), C.byref(created)), "hk_scene_bvh_cost")
         return now.value, created.value
 
+    def rebuild_bvh(self, ctx=None, costs=True):
+        """hk_scene_rebuild_bvh for every device scene created from this Scene (ctx=None), or for that context's alone: the BVH is
+        built anew on the device from the world positions it holds, the tree hk_scene_create would build from them; everything else
+        of the scene stays.  -> [(cost_before, cost_after)] per device scene touched (one pair for a given ctx): the tree cost
+        (bvh_cost) the refits had left, and the cost of the new tree — the baseline of bvh_cost from now on.
+
+        The library call waits for the device once.  The two cost read-outs around it wait too (one reduction and one wait each):
+        costs=False skips them and returns [None] per device scene — the call an interactive loop wants."""
+        from . import _lib, volpath
+        if ctx is not None:
+            handles = [volpath.scene_handle(ctx, self)]
+        else:
+            handles = list((getattr(self, "_device", None) or {}).values())
+        out = []
+        for h in handles:
+            before, after = C.c_double(), C.c_double()
+            if costs:
+                _lib.check(_lib.lib().hk_scene_bvh_cost(h, C.byref(before), None), "hk_scene_bvh_cost")
+            _lib.check(_lib.lib().hk_scene_rebuild_bvh(h), "hk_scene_rebuild_bvh")
+            if costs:
+                _lib.check(_lib.lib().hk_scene_bvh_cost(h, None, C.byref(after)), "hk_scene_bvh_cost")
+            out.append((before.value, after.value) if costs else None)
+        return out
+
+    def bvh_leaves(self, ctx):
+        """The triangle index of every leaf slot of this scene's BVH on `ctx` (hk_scene_bvh_leaves), int32 [n_triangles]: what the
+        leaf references of hk_scene_bvh_copy (~ref = first slot << 3 | count - 1) index."""
+        from . import _lib, volpath
+        h = volpath.scene_handle(ctx, self)
+        n = C.c_int32()
+        _lib.check(_lib.lib().hk_scene_bvh_leaves(h, C.byref(n), None), "hk_scene_bvh_leaves")
+        prims = np.empty(n.value, np.int32)
+        if n.value:
+            _lib.check(_lib.lib().hk_scene_bvh_leaves(h, C.byref(n), prims.ctypes.data_as(C.POINTER(C.c_int32))), "hk_scene_bvh_leaves")
+        return prims
+
     # ---- lights and environment maps in place (hk_scene_update_lights, hk_scene_update_envmap) --------------------------------
     def _flat_index(self, index):
         light = self.lights[index]

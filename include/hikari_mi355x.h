@@ -668,6 +668,26 @@ int32_t hk_scene_bvh_cost(hk_scene* scene, double* cost_now, double* cost_create
    node (lo0[3] hi0[3] lo1[3] hi1[3]), refs = the two child references (>= 0: an inner node; < 0: ~ref = first leaf slot << 3 | count - 1).
    Waits for the context's stream.  Either array may be NULL. */
 int32_t hk_scene_bvh_copy(hk_scene* scene, int32_t* n_nodes, float* boxes /* 12 per node: lo0 hi0 lo1 hi1 */, int32_t* refs /* 2 per node */);
+/* The triangle index of every leaf slot, in the order of the leaf records (the slots the leaf references of hk_scene_bvh_copy count):
+   *n = the number of slots (the scene's triangle count), prims (NULL: only *n) = n indices.  Waits for the context's stream. */
+int32_t hk_scene_bvh_leaves(hk_scene* scene, int32_t* n, int32_t* prims);
+/* Rebuilds the triangle BVH on the device from the world positions the device holds (under every hk_scene_set_transform and
+   hk_scene_set_vertices in force): the tree hk_scene_create would build from those positions now — the same binned-SAH decision per
+   node (one function for both builders), leaf size and bin count of the context's HK_BVH_LEAF / HK_BVH_BINS as of this call — so node
+   count, depth, every child reference, the set of triangles of every leaf and every box are the fresh scene's.  (Exception: a node
+   that takes the builder's median fallback — all centroids coincide, or the depth budget of 30 levels refuses the SAH split — is cut at
+   count / 2 in both builders, but the device keeps the segment's order where the host selects by centroid: other triangles may land
+   on either side, and the subtree below a node the depth budget cut may differ.)  The order of the triangles INSIDE a leaf is the device builder's.  Hits, and therefore
+   films, do not depend on the tree.
+   Like every edit the call renders the noted calls first, joins the lanes and enqueues on the context's stream; unlike the others it
+   WAITS FOR THE DEVICE ONCE, for the node count, the depth and the level table of the new tree.  Geometry, transforms, materials,
+   lights, media, films and the view cache stay as they are; cost_created of hk_scene_bvh_cost becomes the cost of the tree just built
+   (the new baseline of the drift), and cost_now equals it.  The depth may cross 16 in either direction: the traversal kernels are chosen
+   per render call from the depth the scene has then.  A scene whose root is a leaf (no inner node) is left as it is: HK_OK.
+   HK_BVH_BUILD_SMALL (context option, default 1024): nodes of at most that many triangles are binned by one block in LDS, larger ones
+   by many blocks through integer atomics; the tree does not depend on it.
+   The tree is built into new buffers that replace the old ones at the end: a failing call leaves the scene as it was. */
+int32_t hk_scene_rebuild_bvh(hk_scene* scene);
 
 /* The majorant grid (n_cells floats, index x + rx*(y + ry*z)) and the zero-cell mask ((n_cells + 31) / 32 words, bit c of the mask = cell c)
    of medium `idx` as the device holds them; waits for the context's stream.  Either array may be NULL; n_cells = 0 for a homogeneous medium. */

@@ -758,6 +758,41 @@ function bvh_cost(vp::MI355XVolPath)
     (now[], created[])
 end
 
+"""
+    rebuild_bvh!(vp)
+
+Rebuilds the triangle BVH of every device scene from the world positions the device holds (under every `set_transform!` /
+`set_vertices!` in force): the tree a freshly created scene would get.  Everything else of the scene stays; `bvh_cost` afterwards
+reports the new tree as its baseline.  The one edit that waits for the device (once, for the size of the new tree).
+"""
+function rebuild_bvh!(vp::MI355XVolPath)
+    for d in vp.devs
+        d.scene == C_NULL && continue
+        check(ccall((:hk_scene_rebuild_bvh, LIB), Int32, (Ptr{Cvoid},), d.scene), "hk_scene_rebuild_bvh")
+    end
+    nothing
+end
+
+"""
+    bvh_leaves(vp) -> Vector{Int32}
+
+The 0-based triangle index of every leaf slot of the scene's BVH on the first device, in the order of the leaf records.
+"""
+function bvh_leaves(vp::MI355XVolPath)
+    prims = Int32[]
+    for d in vp.devs
+        d.scene == C_NULL && continue
+        n = Ref{Int32}(0)
+        check(ccall((:hk_scene_bvh_leaves, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}, Ptr{Int32}), d.scene, n, Ptr{Int32}(C_NULL)), "hk_scene_bvh_leaves")
+        prims = Vector{Int32}(undef, n[])
+        GC.@preserve prims begin
+            check(ccall((:hk_scene_bvh_leaves, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}, Ptr{Int32}), d.scene, n, pointer(prims)), "hk_scene_bvh_leaves")
+        end
+        break
+    end
+    prims
+end
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # postprocess! / denoise! / fill_aux_buffers! forwards (postprocess.jl:293-357, denoise.jl:301-376, film.jl:410-483)
 # ---------------------------------------------------------------------------------------------------------------------------
