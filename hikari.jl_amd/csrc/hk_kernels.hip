@@ -2613,8 +2613,16 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(BLOCK, BLOCK), amdgpu
 #ifndef HK_SHADE_WAVES
 #define HK_SHADE_WAVES 3
 #endif
+#ifndef HK_SHADE_WAVES_LEAN   // the LEAN Matte instantiation (shade_body) whose draws are table loads
+#define HK_SHADE_WAVES_LEAN 5
+#endif
+#ifndef HK_SHADE_WAVES_LEAN_HASH   // the LEAN instantiation with the digit-hashing fallback in it
+#define HK_SHADE_WAVES_LEAN_HASH 5
+#endif
 // K8 for one flagged vertex (surface-eval.jl:147-220): L += beta * Le / MIS denominator.
-template <bool TWO_PLANES, bool SIMPLE>
+// LEAN (shade_body): the generation records are compact with 32-bit meta words and r_u == 1 — the weights are one float each, the
+// same additions in the same order (the four equal components of the general form are summed one by one: 3a + a is not 4a in binary32)
+template <bool TWO_PLANES, bool SIMPLE, bool LEAN = false>
 HKD void shade_emission(const DPathState& st, const DPathGen& g, bool ones, const DScene& sc, const DTables& T, uint32_t slot, unsigned& n_lnodes, int depth, size_t seg) {
     const float4 H = st.hit[slot];
     const float4 O = ld_ray_o(st, g, slot, depth, seg), D = g.ray_d[slot];
@@ -2625,35 +2633,59 @@ HKD void shade_emission(const DPathState& st, const DPathGen& g, bool ones, cons
     if (meta.arealight <= 0) return;
     const Surface sf = surface_at(sc, prim, H.z, H.w, ro, rd, t_hit);
     const v3 wo = -rd;
-    const uint2 pmeta = ld_meta(st, g, slot, depth);
+    uint2 pmeta;
+    if constexpr (LEAN) {
+        const uint32_t w = reinterpret_cast<const uint32_t*>(g.meta)[slot];
+        pmeta = make_uint2((uint32_t)depth | (((w >> 30) & 1u) << 8), w & 0x3fffffffu);
+    } else
+        pmeta = ld_meta(st, g, slot, depth);
     const S4 lambda = ld_lambda(st, g, slot, pmeta.y);
     const DLight& light = sc.lights[meta.arealight - 1];
     S4 Le = arealight_Le<TWO_PLANES, SIMPLE>(sc, T, light, wo, sf.n, sf.uv, lambda);
     if (is_black(Le)) return;
-    const S4 beta = ld_throughput(g.beta, slot, ones), r_u = ld_ru(g, slot, ones, st.compact != 0), r_l = ld_rl(g, slot, ones, st.compact != 0);
+    const S4 beta = ld_throughput(g.beta, slot, ones);
     const uint32_t fl = pmeta.x;
     const int pdepth = (int)(fl & 0xff);
     const bool specular_bounce = (fl >> 8) & 1u;
     S4 contribution = beta * Le;
     S4 fin;
-    if (pdepth == 0 || specular_bounce)
-        fin = contribution / average(r_u);
-    else {
-        float choice = bvh_pmf(sc, sf.pi, sf.n, (int)meta.arealight, n_lnodes);
-        float ct = fabsf(dot(sf.n, normalize(rd)));
-        float light_pdf = 0.0f;
-        if (ct > 0.0f && sf.area > 0.0f) light_pdf = choice * ((t_hit * t_hit) / (ct * sf.area));
-        S4 rl = r_l * light_pdf;
-        float den = average(r_u + rl);
-        fin = den > 1e-10f ? contribution / den : contribution / average(r_u);
+    if constexpr (LEAN) {
+        // average(r_u) == (((1 + 1) + 1) + 1) / 4 == 1 and x / 1 == x
+        fin = contribution;
+        if (!(pdepth == 0 || specular_bounce)) {
+            const float r_l = ones ? 1.0f : D.w;   // (compact: r_l travels in the fourth word of ray_d)
+            float choice = bvh_pmf(sc, sf.pi, sf.n, (int)meta.arealight, n_lnodes);
+            float ct = fabsf(dot(sf.n, normalize(rd)));
+            float light_pdf = 0.0f;
+            if (ct > 0.0f && sf.area > 0.0f) light_pdf = choice * ((t_hit * t_hit) / (ct * sf.area));
+            const float a = 1.0f + r_l * light_pdf;
+            const float den = (((a + a) + a) + a) / 4.0f;
+            if (den > 1e-10f) fin = contribution / den;
+        }
+    } else {
+        const S4 r_u = ld_ru(g, slot, ones, st.compact != 0), r_l = ld_rl(g, slot, ones, st.compact != 0);
+        if (pdepth == 0 || specular_bounce)
+            fin = contribution / average(r_u);
+        else {
+            float choice = bvh_pmf(sc, sf.pi, sf.n, (int)meta.arealight, n_lnodes);
+            float ct = fabsf(dot(sf.n, normalize(rd)));
+            float light_pdf = 0.0f;
+            if (ct > 0.0f && sf.area > 0.0f) light_pdf = choice * ((t_hit * t_hit) / (ct * sf.area));
+            S4 rl = r_l * light_pdf;
+            float den = average(r_u + rl);
+            fin = den > 1e-10f ? contribution / den : contribution / average(r_u);
+        }
     }
     st4(&st.L[pmeta.y], ld4(&st.L[pmeta.y]) + fin);
 }
 
 template <int KIND>
 struct ShadeWaves {
-    // Matte runs faster at 4 waves per SIMD with 224 B of scratch than at 3 with 48 B (Cornell k_shade -5 %); the kinds with larger
-    // BSDFs lose more to the spills than the fourth wave returns (sky: conductor + glass +7 %)
+    // Matte runs faster at 4 waves per SIMD with some scratch than at 3 without (Cornell: the scratch-free three-wave build of
+    // k_shade<Matte, SIMPLE, FT> is 19 % slower, 42.6 -> 50.6 ms per frame).  By the compiler's listing k_shade<Matte, SIMPLE, FT> holds
+    // 128 VGPRs + 28 B of scratch per lane at 4 waves (96 + 156 B at 5), k_shade<Matte, SIMPLE, !FT> 128 + 76 B (96 + 220 B at 5): the
+    // fifth wave is the LEAN instantiation's (shade_body), which fits 96 registers.  The kinds with larger BSDFs lose more to the
+    // spills than the fourth wave returns (sky: conductor + glass +7 %)
     static constexpr int value = (KIND == HK_MAT_COATED_DIFFUSE || KIND == HK_MAT_COATED_DIFFUSE_TRANSMISSION) ? 1 : (KIND == HK_MAT_MATTE ? HK_SHADE_WAVES_MATTE : HK_SHADE_WAVES);
 };
 #ifndef HK_SHADE_MIN_WAVES
@@ -2665,22 +2697,44 @@ struct ShadeWaves {
 // hash loops inlined at each of the five draw sites — is not in the kernel at all.
 // PRE: the light of this vertex's next-event estimation was chosen by k_light_select (scenes with a deep light BVH): the descent —
 // three quarters of this kernel's time in the 5*10^4-light scene, run at 49 % lane utilisation because leaf depths differ — is not here.
-template <int KIND, bool SIMPLE, bool FT, bool PRE>
+// LEAN (Matte; the launcher: compact && meta32 && sh_final state in a lean_scene): what those run-time facts fix is fixed at compile
+// time.  r_u is the constant 1 (neither loaded nor kept), the MIS weights are one float each, there is no medium and no interface
+// record, the meta word is the 32-bit one, the slim shadow record the only one.  Only exact folds (1 * x, x / 1, component .x): the
+// films are those of the general instantiation bit for bit.  The values that only the second half of a vertex reads (K11 and the
+// BSDF evaluation at the end of K9) wait in `stash` — HK_SHADE_STASH dwords per lane of LDS, [dword][thread of the block] — while the
+// light is chosen and sampled: with them out of the register file the kernel fits 96 registers, five waves per SIMD.
+#define HK_SHADE_STASH 16
+template <int KIND, bool SIMPLE, bool FT, bool PRE, bool LEAN = false>
 __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& sc, const DTables& T, const DFrame& fr, const DSobol& sob, int depth, int first_kind, DStats* stats, const SegTickets& src,
-                                           uint32_t* __restrict__ elist) {   // elist: this wave's 128 LDS words (slots of flagged — emissive-hit — vertices waiting for the dense K8 pass)
+                                           uint32_t* __restrict__ elist,   // elist: this wave's 128 LDS words (slots of flagged — emissive-hit — vertices waiting for the dense K8 pass)
+                                           float* stash = nullptr) {       // LEAN: the block's HK_SHADE_STASH * 256 LDS words
+    static_assert(!LEAN || (KIND == HK_MAT_MATTE && HK_LAMBDA_BY_SLOT), "the lean body is Matte's");
     const int lane = lane_id();
     unsigned n_vertices = 0, n_lnodes = 0;
-    HK_FOR_EACH_SEGMENT_FROM(gw, st, src) {
+    unsigned nv_wave = 0;   // LEAN: the vertices of the whole wave
+    // LEAN: the per-lane count of light-BVH nodes lives in the last stash word between the chunks
+    unsigned* const nl_stash = LEAN ? reinterpret_cast<unsigned*>(stash) + (HK_SHADE_STASH - 1) * 256 + threadIdx.x : nullptr;
+    auto nl_flush = [&]() {
+        if constexpr (LEAN) {
+            if (n_lnodes) *nl_stash += n_lnodes;
+            n_lnodes = 0;
+        }
+    };
+    if constexpr (LEAN) *nl_stash = 0u;
+    // LEAN: what is the same for the whole wave (segment, counts) is said to be (readfirstlane): it lives in scalar registers
+    auto uni = [](int v) { return LEAN ? __builtin_amdgcn_readfirstlane(v) : v; };
+    HK_FOR_EACH_SEGMENT_FROM(gw_v, st, src) {
+    const int gw = uni(gw_v);
     const uint32_t* __restrict__ queue = st.mat_q + ((size_t)KIND * st.n_waves + gw) * st.wave_cap;
-    const int n = *count_ptr(st, depth, Q_MAT0 + KIND, gw);
+    const int n = uni(*count_ptr(st, depth, Q_MAT0 + KIND, gw));
     const DPathGen g = gen_at(st, depth), gn = st.gen[(depth + 1) & 1];
     const size_t seg = (size_t)gw * st.wave_cap;
     const bool ones = depth == 0 && fr.implicit_ones;
     // several kinds append to the same shadow-record / next-generation segments: continue from the counts left by the kinds before
     WavePos q_shadow{0}, q_next{0};
     if (!first_kind) {
-        q_shadow.count = *count_ptr(st, depth, Q_SHADOW, gw);
-        q_next.count = *count_ptr(st, depth + 1, Q_RAY, gw);
+        q_shadow.count = uni(*count_ptr(st, depth, Q_SHADOW, gw));
+        q_next.count = uni(*count_ptr(st, depth + 1, Q_RAY, gw));
     }
     // ---- K8 first, densely: emission from area-light hits, MIS against the light-BVH pmf (surface-eval.jl:147-220).  The trace
     //      kernels flag such hits in mat_id; their entries are gathered in a wave-private LDS list and handled 64 at a time.  Done
@@ -2700,7 +2754,8 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
             }
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
             const int take = n_emit < 64 ? n_emit : 64;
-            if (lane < take) shade_emission<KIND == HK_MAT_MATTE, SIMPLE>(st, g, ones, sc, T, elist[lane], n_lnodes, depth, seg);
+            if (lane < take) shade_emission<KIND == HK_MAT_MATTE, SIMPLE, LEAN>(st, g, ones, sc, T, elist[lane], n_lnodes, depth, seg);
+            nl_flush();
             const int rest = n_emit - take;
             const uint32_t moved = lane < rest ? elist[64 + lane] : 0u;
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -2723,13 +2778,22 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
         int pdepth = 0, medium = -1;
         bool any_non_specular = false;
         SobolCtx sctx;
+        using W = std::conditional_t<LEAN, float, S4>;   // a MIS weight
+        // LEAN: this lane's column of the stash, [dword][thread]; stash_at launders the index so that no store is forwarded to a load
+        auto stash_at = [&]() {
+            int i = (int)threadIdx.x;
+            asm volatile("" : "+v"(i));
+            return stash + i;
+        };
         // every path in the depth-d queues has work.depth == d, so the dimension (and its scramble hashes) is
         // wave-uniform: derived from the kernel argument it stays in scalar registers
         const int base_dim = 6 + 7 * depth;
         float4 shO = make_float4(0, 0, 0, 0), shD = shO;
-        S4 shLd = s4(0.0f), shRu = s4(0.0f), shRl = s4(0.0f);
+        S4 shLd = s4(0.0f);
+        W shRu{}, shRl{};
+        if constexpr (LEAN) nv_wave += (unsigned)(n - base < 64 ? n - base : 64);   // (wave-uniform: a scalar register)
         if (active) {
-            ++n_vertices;
+            if constexpr (!LEAN) ++n_vertices;
             H = stream_ld(&st.hit[slot]);
             float4 O = ld_ray_o(st, g, slot, depth, seg), D = stream_ld(&g.ray_d[slot]);
             v3 ro = mk3(O.x, O.y, O.z), rd = mk3(D.x, D.y, D.z);
@@ -2738,20 +2802,28 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
             sf = surface_at(sc, prim, H.z, H.w, ro, rd, t_hit);
             wo = -rd;
             meta = tri_meta(sc, prim);
-            const uint2 pmeta = ld_meta(st, g, slot, depth);
-            lambda = ld_lambda(st, g, slot, pmeta.y);
+            uint32_t meta_w = 0;   // LEAN: the record's 32-bit meta word (path slot, specular and any-non-specular bits)
+            if constexpr (LEAN) {
+                meta_w = reinterpret_cast<const uint32_t*>(g.meta)[slot];
+                pslot = meta_w & 0x3fffffffu;
+                pdepth = depth;   // (what ld_meta returns for a 32-bit word: every path of the depth-d queues is at depth d)
+                any_non_specular = (meta_w >> 31) != 0u;
+            } else {
+                const uint2 pmeta = ld_meta(st, g, slot, depth);
+                fl = pmeta.x;
+                pslot = pmeta.y;
+                pdepth = (int)(fl & 0xff);
+                any_non_specular = (fl >> 9) & 1u;
+                medium = (int)(fl >> 16) - 1;
+                r_u = ld_ru(g, slot, ones, st.compact != 0);
+            }
+            lambda = ld_lambda(st, g, slot, pslot);
             if (ones)
                 beta = s4(1.0f);
             else {
                 const float4 bv = stream_ld(&g.beta[slot]);
                 beta = s4(bv.x, bv.y, bv.z, bv.w);
             }
-            r_u = ld_ru(g, slot, ones, st.compact != 0);
-            fl = pmeta.x;
-            pslot = pmeta.y;
-            pdepth = (int)(fl & 0xff);
-            any_non_specular = (fl >> 9) & 1u;
-            medium = (int)(fl >> 16) - 1;
 
             // pixel coordinates for the Sobol dimensions of this bounce (volpath.jl:252-262, Q19)
             int pix, k;
@@ -2811,6 +2883,14 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
             }
 #endif
 
+            if constexpr (LEAN) {   // out of the registers while the light is chosen and sampled
+                float* sp = stash + threadIdx.x;
+                sp[0 * 256] = sf.n.x, sp[1 * 256] = sf.n.y, sp[2 * 256] = sf.n.z;
+                sp[3 * 256] = wo.x, sp[4 * 256] = wo.y, sp[5 * 256] = wo.z;
+                sp[6 * 256] = kd_matte.x, sp[7 * 256] = kd_matte.y, sp[8 * 256] = kd_matte.z, sp[9 * 256] = kd_matte.w;
+                sp[10 * 256] = beta.x, sp[11 * 256] = beta.y, sp[12 * 256] = beta.z, sp[13 * 256] = beta.w;
+                sp[14 * 256] = __uint_as_float(meta_w);
+            }
             // ---- K9: next-event estimation through the light BVH ----
             if (sc.n_lights > 0) {
                 const DMaterial& mat = sc.materials[st.mat_id[slot] & ~HK_MAT_EMISSIVE_BIT];
@@ -2832,6 +2912,12 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
                     LightSample ls = sample_light<KIND == HK_MAT_MATTE, SIMPLE>(sc, T, sel, sf.pi, lambda, u_light);
                     if (ls.pdf > 0.0f && !is_black(ls.Li)) {
                         float bsdf_pdf;
+                        if constexpr (LEAN) {
+                            const float* sp = stash_at();
+                            wo = mk3(sp[3 * 256], sp[4 * 256], sp[5 * 256]);
+                            kd_matte = s4(sp[6 * 256], sp[7 * 256], sp[8 * 256], sp[9 * 256]);
+                            beta = s4(sp[10 * 256], sp[11 * 256], sp[12 * 256], sp[13 * 256]);
+                        }
                         S4 f = KIND == HK_MAT_MATTE ? eval_matte_kd(kd_matte, wo, ls.wi, sf.ns, bsdf_pdf)
                                                     : eval_bsdf<KIND>(sc, T, mat, wo, ls.wi, sf.ns, TexCtx(sf.uv, meta.prim_index, H.z, H.w), lambda, bsdf_pdf);
                         if (!is_black(f)) {
@@ -2846,8 +2932,13 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
                                 shO = make_float4(so.x, so.y, so.z, tmax);
                                 shD = make_float4(ls.wi.x, ls.wi.y, ls.wi.z, __int_as_float(medium));
                                 shLd = Ld;
-                                shRu = r_u * nbp;
-                                shRl = (r_u * ls.pdf) * light_pmf;
+                                if constexpr (LEAN) {   // r_u == 1
+                                    shRu = nbp;
+                                    shRl = ls.pdf * light_pmf;
+                                } else {
+                                    shRu = r_u * nbp;
+                                    shRl = (r_u * ls.pdf) * light_pmf;
+                                }
                                 push_shadow = true;
                             }
                         }
@@ -2855,10 +2946,20 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
                 }
             }
         }
+        nl_flush();
         // the shadow record goes to its position in the segment's shadow queue: k_shadow streams the records
         {
             const size_t ps = seg + (size_t)wp_push(q_shadow, push_shadow);
-            if (push_shadow && st.sh_final) {   // slim record (shadow_contribute_final): the denominator beside the direction instead of two weights
+            if constexpr (LEAN) {   // the slim record is the only one; its denominator by the general form's additions, in their order
+                if (push_shadow) {
+                    const float m = shRu + shRl;
+                    shD.w = (((m + m) + m) + m) / 4.0f;
+                    stream_st(&st.sh_o[ps], shO);
+                    stream_st(&st.sh_d[ps], shD);
+                    stream_st(&st.sh_Ld[ps], shLd);
+                    stream_st(&st.sh_slot[ps], pslot);
+                }
+            } else if (push_shadow && st.sh_final) {   // slim record (shadow_contribute_final): the denominator beside the direction instead of two weights
                 const S4 mis = s4(shRu.x) * s4(1.0f) + s4(shRl.x) * s4(1.0f);
                 shD.w = average(mis);
                 stream_st(&st.sh_o[ps], shO);
@@ -2882,13 +2983,28 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
         }
         // ---- K11: BSDF sampling, throughput, Russian roulette, continuation ray ----
         float4 nO = make_float4(0, 0, 0, 0), nD = nO;
-        S4 nb = s4(0.0f), nrl = s4(0.0f);
+        S4 nb = s4(0.0f);
+        W nrl{};
         uint32_t nflags = 0;
         if (active) {
             int new_depth = pdepth + 1;
             if (new_depth < fr.max_depth) {
                 const DMaterial& mat = sc.materials[st.mat_id[slot] & ~HK_MAT_EMISSIVE_BIT];
-                const DMediumInterface mi = sc.mis[meta.mi];
+                DMediumInterface mi{};
+                if constexpr (LEAN) {   // back from the stash; the sampler context is derived again from the path slot (the same values)
+                    const float* sp = stash_at();
+                    sf.n = mk3(sp[0 * 256], sp[1 * 256], sp[2 * 256]);
+                    wo = mk3(sp[3 * 256], sp[4 * 256], sp[5 * 256]);
+                    kd_matte = s4(sp[6 * 256], sp[7 * 256], sp[8 * 256], sp[9 * 256]);
+                    beta = s4(sp[10 * 256], sp[11 * 256], sp[12 * 256], sp[13 * 256]);
+                    const uint32_t meta_w = __float_as_uint(sp[14 * 256]);
+                    pslot = meta_w & 0x3fffffffu;
+                    any_non_specular = (meta_w >> 31) != 0u;
+                    int pix, k;
+                    split_slot(fr, pslot, pix, k);
+                    sctx = sobol_ctx_slot(sob, T.sobol, fr.x0, fr.y0, fr.tiles_x, pix, k, fr.first_sample + k * fr.sample_stride);
+                } else
+                    mi = sc.mis[meta.mi];
                 // the 1-D component sample is read only by BSDFs that choose a lobe (Glass and the layered kinds)
                 float uc = (KIND == HK_MAT_GLASS || KIND > HK_MAT_CONDUCTOR) && KIND != HK_MAT_FALLBACK ? sobol_1d<FT>(sctx, base_dim + 4) : 0.0f;
                 v2 u = (KIND == HK_MAT_MIRROR || KIND == HK_MAT_GLASS || KIND == HK_MAT_THIN_DIELECTRIC) ? mk2(0.0f, 0.0f) : sobol_2d<FT>(sctx, base_dim + 6);
@@ -2898,7 +3014,8 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
                 if (s.pdf > 0.0f && !is_black(s.f)) {
                     float ct = fabsf(dot(s.wi, sf.ns));
                     nb = s.is_specular ? beta * s.f : beta * s.f * ct / s.pdf;
-                    nrl = s.is_specular ? r_u : r_u / s.pdf;
+                    if constexpr (LEAN) nrl = s.is_specular ? 1.0f : 1.0f / s.pdf;   // r_u == 1
+                    else nrl = s.is_specular ? r_u : r_u / s.pdf;
                     bool cont = true;
                     if (new_depth > 3) {  // russian_roulette_spectral, min_depth fixed at 3 (Q7)
                         float rr = sobol_1d<FT>(sctx, base_dim + 7);
@@ -2909,7 +3026,8 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
                             nb = nb * (1.0f / (1.0f - q));
                     }
                     if (cont) {
-                        int new_medium = (mi.inside != mi.outside) ? (dot(s.wi, sf.n) > 0.0f ? mi.outside : mi.inside) : medium;
+                        int new_medium = -1;   // LEAN: no interface changes the medium, and -1 + 1 leaves the flag word's medium field 0
+                        if constexpr (!LEAN) new_medium = (mi.inside != mi.outside) ? (dot(s.wi, sf.n) > 0.0f ? mi.outside : mi.inside) : medium;
                         v3 off = dot(s.wi, sf.n) > 0.0f ? sf.n : -sf.n;
                         v3 no = sf.pi + off * 0.0001f;
                         nO = make_float4(no.x, no.y, no.z, INF_F);
@@ -2923,7 +3041,15 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
         }
         {   // the continuing path's record, whole, at its position in the next generation (r_u is unchanged by a surface event)
             const size_t pn = seg + (size_t)wp_push(q_next, push_ray);
-            if (push_ray) {
+            if constexpr (LEAN) {   // the compact record with its 32-bit meta word
+                if (push_ray) {
+                    stream_st(&gn.ray_o[pn], nO);
+                    nD.w = nrl;
+                    stream_st(&gn.ray_d[pn], nD);
+                    stream_st(&gn.beta[pn], nb);
+                    stream_st(reinterpret_cast<uint32_t*>(gn.meta) + pn, pslot | (((nflags >> 8) & 1u) << 30) | (((nflags >> 9) & 1u) << 31));
+                }
+            } else if (push_ray) {
                 stream_st(&gn.ray_o[pn], nO);
                 if (st.compact) nD.w = nrl.x;   // (compact: r_l travels beside the direction)
                 stream_st(&gn.ray_d[pn], nD);
@@ -2939,15 +3065,24 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
         *count_ptr(st, depth + 1, Q_RAY, gw) = q_next.count;
     }
     }
+    if constexpr (LEAN) {
+        n_vertices = lane == 0 ? nv_wave : 0u;   // (the statistics are sums over the lanes)
+        n_lnodes = *nl_stash;
+    }
     stats += global_wave();
     wave_add(&stats->vertices, n_vertices);
     wave_add(&stats->light_nodes, n_lnodes);
 }
-template <int KIND, bool SIMPLE = false, bool FT = false, bool PRE = false>
-__global__ void __attribute__((amdgpu_flat_work_group_size(256, 256), amdgpu_waves_per_eu(ShadeWaves<KIND>::value))) k_shade(DPathState st, DScene sc, DTables T, DFrame fr, DSobol sob, int depth, int first_kind, DStats* stats) {
+template <int KIND, bool SIMPLE = false, bool FT = false, bool PRE = false, bool LEAN = false>
+__global__ void __attribute__((amdgpu_flat_work_group_size(256, 256), amdgpu_waves_per_eu(LEAN ? (FT ? HK_SHADE_WAVES_LEAN : HK_SHADE_WAVES_LEAN_HASH) : ShadeWaves<KIND>::value))) k_shade(DPathState st, DScene sc, DTables T, DFrame fr, DSobol sob, int depth, int first_kind, DStats* stats) {
     __shared__ uint32_t emit_list[4 * 128];
-    shade_body<KIND, SIMPLE, FT, PRE>(st, sc, T, fr, sob, depth, first_kind, stats, seg_open(st, ticket_ptr(st, depth, TK_SHADE0 + KIND), st.dynamic_segments != 0, depth, Q_MAT0 + KIND),
-                                      emit_list + (threadIdx.x >> 6) * 128);
+    SegTickets src = seg_open(st, ticket_ptr(st, depth, TK_SHADE0 + KIND), st.dynamic_segments != 0, depth, Q_MAT0 + KIND);
+    if constexpr (LEAN) {
+        src.pos = __builtin_amdgcn_readfirstlane(src.pos), src.k0 = __builtin_amdgcn_readfirstlane(src.k0);   // (wave-uniform: the wave's index)
+        __shared__ float stash[HK_SHADE_STASH * 256];   // five blocks per CU: 5 x (2 KB + 16 KB) of the CU's 160 KB
+        shade_body<KIND, SIMPLE, FT, PRE, true>(st, sc, T, fr, sob, depth, first_kind, stats, src, emit_list + (threadIdx.x >> 6) * 128, stash);
+    } else
+        shade_body<KIND, SIMPLE, FT, PRE>(st, sc, T, fr, sob, depth, first_kind, stats, src, emit_list + (threadIdx.x >> 6) * 128);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -290,6 +290,13 @@ void launch_shade(hipStream_t s, int n_cu, int kind, const DPathState& st, const
         launch_resident<k_shade<decltype(KIND)::value, decltype(SIMPLE)::value, decltype(FT)::value, decltype(PRE)::value>>(s, n_cu, st, 256, 8, sc, T, fr, sob, depth, first_kind, stats);
     };
     const bool ft = sobol_tables_cover(sob, depth);
+    // Matte under simple lights in a lean scene whose state holds the lean records (compact, 32-bit meta words, the slim shadow record):
+    // the LEAN instantiation — those facts at compile time, the second half's values handed over through LDS, five waves per SIMD
+    // (HK_SHADE_LEAN=0: the general instantiation; A/B switch, films bit-identical)
+    if (kind == HK_MAT_MATTE && sc.simple_lights && lean_scene(sc) && st.compact && st.meta32 && st.sh_final && !preselect_lights(sc, st) && knob_on("HK_SHADE_LEAN")) {
+        with_bool(ft, [&](auto FT) { launch_resident<k_shade<HK_MAT_MATTE, true, decltype(FT)::value, false, true>>(s, n_cu, st, 256, 8, sc, T, fr, sob, depth, first_kind, stats); });
+        return;
+    }
     // the kinds with next-event instantiations of their own (table-only draws, a light chosen beforehand); the others run k_shade<KIND>
     const bool light_kind = kind == HK_MAT_MATTE || kind == HK_MAT_MIRROR || kind == HK_MAT_GLASS || kind == HK_MAT_CONDUCTOR;
     if (light_kind && preselect_lights(sc, st))   // k_light_select has run for this depth: the instantiations without the light-BVH descent
