@@ -598,6 +598,10 @@ HKD NodeCache scene_cache_fill(const DScene& sc, float4* __restrict__ box, int2*
     return c;
 }
 
+// A kind-queue entry (DPathState::mat_q) for a hit whose mat_id word was stored earlier (the media kernels route hits that k_trace
+// recorded): the generation index, with the emissive flag of mat_id in its top bit.
+HKD uint32_t matq_entry(const DPathState& st, uint32_t slot) { return slot | ((st.mat_id[slot] & HK_MAT_EMISSIVE_BIT) != 0 ? HK_MATQ_EMISSIVE : 0u); }
+
 // ---------------------------------------------------------------------------------------------------
 // K3: closest-hit traversal + classification (intersection.jl:188-269).
 // ---------------------------------------------------------------------------------------------------
@@ -685,6 +689,7 @@ __global__ void __launch_bounds__(HK_TRACE_BLOCK) k_trace(DPathState st, DScene 
                 st.hit[slot] = make_float4(h.t, __int_as_float(h.prim), h.u, h.v);
                 st.mat_id[slot] = mat | (meta.arealight > 0 ? HK_MAT_EMISSIVE_BIT : 0);
                 if (it > 0) g.ray_o[slot] = make_float4(ro.x, ro.y, ro.z, INF_F);  // origin after alpha skips
+                if (meta.arealight > 0) slot |= HK_MATQ_EMISSIVE;   // the flag travels in the kind-queue entry (in `slot` itself: a register more costs this kernel its fourth wave; from here on `slot` is a queue ENTRY — it feeds the two pushes below and must not index anything)
                 break;
             }
         }
@@ -964,12 +969,14 @@ __device__ __forceinline__ void trace_lean_body(const DPathState& st, const DSce
             // ---- flush: classify the finished rays, push them to the escaped / material-kind queues ----
             HK_DBG(8, state == LR_ACTIVE && r.cur == DONE);   // flushes: lanes that deliver a finished ray
             int kind = -1;
+            uint32_t eflag = 0u;   // HK_MATQ_EMISSIVE when the hit triangle carries an area light: travels in the kind-queue entry
             if (state == LR_ACTIVE && r.cur == DONE) {
                 if (r.best.prim < 0)
                     kind = -2;
                 else {
                     ++n_hits;
                     const DTriMeta hm = sc.meta[r.best.prim];
+                    eflag = hm.arealight > 0 ? HK_MATQ_EMISSIVE : 0u;
                     int mat = sc.mis[hm.mi].material;
                     if (sc.materials[mat].kind == HK_MAT_MIX) {   // MixMaterial is resolved here so the queue is sorted by the final kind
                         float w = 1.0f - r.best.u - r.best.v;
@@ -992,7 +999,7 @@ __device__ __forceinline__ void trace_lean_body(const DPathState& st, const DSce
                 int cnt = 0;
 #pragma unroll
                 for (int kk = 0; kk < HK_MAX_KINDS; ++kk) cnt = (kk == k) ? kind_count[kk] : cnt;
-                if (mine) stream_st(&st.mat_q[((size_t)k * st.n_waves + gw) * st.wave_cap + cnt + __popcll(m & lt_mask)], slot);
+                if (mine) stream_st(&st.mat_q[((size_t)k * st.n_waves + gw) * st.wave_cap + cnt + __popcll(m & lt_mask)], slot | eflag);
                 int add = __popcll(m);
 #pragma unroll
                 for (int kk = 0; kk < HK_MAX_KINDS; ++kk) kind_count[kk] += (kk == k) ? add : 0;
@@ -1166,7 +1173,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256, 256), amdgpu_wav
                         int cnt = 0;
 #pragma unroll
                         for (int kk = 0; kk < HK_MAX_KINDS; ++kk) cnt = (kk == k) ? S.kind_count[kk] : cnt;
-                        if (mine) st.mat_q[((size_t)k * st.n_waves + S.gw) * st.wave_cap + cnt + __popcll(m & lt_mask)] = slot;
+                        if (mine) st.mat_q[((size_t)k * st.n_waves + S.gw) * st.wave_cap + cnt + __popcll(m & lt_mask)] = matq_entry(st, slot);
                         int add = __popcll(m);
 #pragma unroll
                         for (int kk = 0; kk < HK_MAX_KINDS; ++kk) S.kind_count[kk] += (kk == k) ? add : 0;
@@ -1508,7 +1515,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256, 256), amdgpu_wav
                     int cnt = 0;
 #pragma unroll
                     for (int kk = 0; kk < HK_MAX_KINDS; ++kk) cnt = (kk == k) ? S.kind_count[kk] : cnt;
-                    if (mine) st.mat_q[((size_t)k * st.n_waves + S.gw) * st.wave_cap + cnt + __popcll(m & lt_mask)] = slot;
+                    if (mine) st.mat_q[((size_t)k * st.n_waves + S.gw) * st.wave_cap + cnt + __popcll(m & lt_mask)] = matq_entry(st, slot);
                     int add = __popcll(m);
 #pragma unroll
                     for (int kk = 0; kk < HK_MAX_KINDS; ++kk) S.kind_count[kk] += (kk == k) ? add : 0;
@@ -1758,7 +1765,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256, 256), amdgpu_wav
         wave_lds_fence();
         const bool have = lane < cnt;
         const int p = (res_head + lane) & (TP_RING - 1);
-        uint32_t rslot = 0;
+        uint32_t rslot = 0, eflag = 0u;
         int key = -1;
         if (have) {
             rslot = (uint32_t)ring[p];
@@ -1774,6 +1781,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256, 256), amdgpu_wav
             int cls = 0;
             if (prim >= 0) {
                 const int mat_word = st.mat_id[rslot];
+                eflag = (mat_word & HK_MAT_EMISSIVE_BIT) != 0 ? HK_MATQ_EMISSIVE : 0u;   // (a surface hit: its destination below is a kind queue)
                 int mat = mat_word & ~HK_MAT_EMISSIVE_BIT;
                 if (sc.materials[mat].kind == HK_MAT_MIX) {
                     const float4 O = g.ray_o[rslot], D = g.ray_d[rslot];
@@ -1798,7 +1806,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256, 256), amdgpu_wav
             uint32_t* __restrict__ q = cls == 0 ? st.escaped_q + (size_t)gw * st.wave_cap
                                      : cls == 1 ? st.scatter_q + (size_t)gw * st.wave_cap
                                                 : st.mat_q + ((size_t)(cls - 2) * st.n_waves + gw) * st.wave_cap;
-            if (key == k) q[base + __popcll(m & lt_mask)] = rslot;
+            if (key == k) q[base + __popcll(m & lt_mask)] = rslot | eflag;
             if (lane == 0) segc[k] = base + __popcll(m);
             todo &= ~m;
         }
@@ -2312,7 +2320,7 @@ __global__ void __launch_bounds__(256) k_light_select(DPathState st, DScene sc, 
                 const int avail = n - cursor;
                 const int rank = __popcll(want & lt_mask);
                 if (!busy && rank < avail) {
-                    slot = queue[cursor + rank];
+                    slot = queue[cursor + rank] & ~HK_MATQ_EMISSIVE;
                     const float4 H = st.hit[slot], O = ld_ray_o(st, g, slot, depth, (size_t)gw * st.wave_cap), D = g.ray_d[slot];
                     const Surface sf = surface_at(sc, __float_as_int(H.y), H.z, H.w, mk3(O.x, O.y, O.z), mk3(D.x, D.y, D.z), H.x);
                     p = sf.pi;
@@ -2496,7 +2504,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(BLOCK, BLOCK), amdgpu
                     float u_b = 0.0f;
                     v3 sp = mk3(0, 0, 0), sn = mk3(0, 0, 1);
                     if (lane < take) {
-                        e = queue[cursor + lane];
+                        e = queue[cursor + lane] & ~HK_MATQ_EMISSIVE;
                         const float4 H = st.hit[e], O = ld_ray_o(st, g, e, depth, (size_t)gw * st.wave_cap), D = g.ray_d[e];
                         const Surface sf = surface_at(sc, __float_as_int(H.y), H.z, H.w, mk3(O.x, O.y, O.z), mk3(D.x, D.y, D.z), H.x);
                         sp = sf.pi;
@@ -2704,10 +2712,30 @@ struct ShadeWaves {
 // BSDF evaluation at the end of K9) wait in `stash` — HK_SHADE_STASH dwords per lane of LDS, [dword][thread of the block] — while the
 // light is chosen and sampled: with them out of the register file the kernel fits 96 registers, five waves per SIMD.
 #define HK_SHADE_STASH 16
+// LEAN, HK_SHADE_PREFETCH: the next chunk's records wait in LDS, fetched by global->LDS loads (no register holds anything across the
+// loop body).  [part][thread of the block]; a wave's 64 lanes own 64 consecutive entries of every part: the LDS base of a load is
+// wave-uniform, the hardware adds lane * size.  entry[chunk & 1]: the queue entry, requested two chunks ahead at the top of a chunk;
+// hit / ray_d / meta: requested one chunk ahead from the middle of a chunk, where the registers are at their lowest, through that entry.
+// 2 * 1 KB + 4 KB + 4 KB + 1 KB = 11 KB beside the 18 KB of list and stash: five blocks per CU still fit (beta, the next in line,
+// would not: 15 KB + 18 KB).
+struct ShadeStage {
+    uint32_t* entry;   // [2][256]
+    float4* hit;       // [256]
+    float4* ray_d;     // [256]
+    uint32_t* meta;    // [256]
+};
+// this lane's 4 / 16 bytes at src -> lds_wave_base[lane]
+__device__ __forceinline__ void lds_fetch4(const uint32_t* src, uint32_t* lds_wave_base) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)lds_wave_base, 4, 0, 0);
+}
+__device__ __forceinline__ void lds_fetch16(const float4* src, float4* lds_wave_base) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
+}
 template <int KIND, bool SIMPLE, bool FT, bool PRE, bool LEAN = false>
 __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& sc, const DTables& T, const DFrame& fr, const DSobol& sob, int depth, int first_kind, DStats* stats, const SegTickets& src,
                                            uint32_t* __restrict__ elist,   // elist: this wave's 128 LDS words (slots of flagged — emissive-hit — vertices waiting for the dense K8 pass)
-                                           float* stash = nullptr) {       // LEAN: the block's HK_SHADE_STASH * 256 LDS words
+                                           float* stash = nullptr,         // LEAN: the block's HK_SHADE_STASH * 256 LDS words
+                                           ShadeStage stage = ShadeStage{}) {   // LEAN: the block's staging area of the fetch-ahead (null pointers: none)
     static_assert(!LEAN || (KIND == HK_MAT_MATTE && HK_LAMBDA_BY_SLOT), "the lean body is Matte's");
     const int lane = lane_id();
     unsigned n_vertices = 0, n_lnodes = 0;
@@ -2736,37 +2764,66 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
         q_shadow.count = uni(*count_ptr(st, depth, Q_SHADOW, gw));
         q_next.count = uni(*count_ptr(st, depth + 1, Q_RAY, gw));
     }
-    // ---- K8 first, densely: emission from area-light hits, MIS against the light-BVH pmf (surface-eval.jl:147-220).  The trace
-    //      kernels flag such hits in mat_id; their entries are gathered in a wave-private LDS list and handled 64 at a time.  Done
-    //      inline in the main pass, a wave walks the light BVH (bvh_pmf, ~2 log2 n node evaluations) whenever ANY of its 64
-    //      vertices sits on an emitter: with 5 % emissive faces that is 96 % of the waves at 5 % lane utilisation. ----
-    {
-        int n_emit = 0;
+    // ---- K8, densely: emission from area-light hits, MIS against the light-BVH pmf (surface-eval.jl:147-220).  The trace kernels
+    //      flag such hits in the kind-queue entry (HK_MATQ_EMISSIVE); the flagged entries are gathered in a wave-private LDS list and
+    //      handled 64 at a time.  Done inline for every vertex, a wave walks the light BVH (bvh_pmf, ~2 log2 n node evaluations)
+    //      whenever ANY of its 64 vertices sits on an emitter: with 5 % emissive faces that is 96 % of the waves at 5 % lane
+    //      utilisation.  The list is fed by the main pass's own queue load and emptied whenever 64 entries wait, and once more after
+    //      the segment's last chunk: an emission add touches L of its own path alone, which nothing else in this kernel reads or
+    //      writes, so where in the launch it happens is free. ----
+    int n_emit = 0;
+    // the first `take` (<= 64) entries of the list; the rest moves to the front
+    auto emit_pass = [&](int take) {
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        if (lane < take) shade_emission<KIND == HK_MAT_MATTE, SIMPLE, LEAN>(st, g, ones, sc, T, elist[lane], n_lnodes, depth, seg);
+        nl_flush();
+        const int rest = n_emit - take;
+        const uint32_t moved = lane < rest ? elist[64 + lane] : 0u;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        if (lane < rest) elist[lane] = moved;
+        n_emit = rest;
+    };
+    const bool prescan = uni(st.shade_prescan) != 0;
+    if (prescan) {
+        // HK_SHADE_PRESCAN=1 (A/B switch; films bit-identical): the flag is looked up in mat_id by a pass of its own over the whole
+        // queue before the first vertex is shaded — two dependent round trips per chunk that the default does not make
         for (int base = 0; base < n || n_emit > 0; base += 64) {
             if (base < n) {
                 const int i = base + lane;
-                const uint32_t cand = i < n ? queue[i] : 0u;
+                const uint32_t cand = i < n ? queue[i] & ~HK_MATQ_EMISSIVE : 0u;
                 const bool em = i < n && (st.mat_id[cand] & HK_MAT_EMISSIVE_BIT) != 0;
                 const unsigned long long m = __ballot(em);
                 if (em) elist[n_emit + __popcll(m & ((1ull << lane) - 1ull))] = cand;
                 n_emit += __popcll(m);
                 if (n_emit < 64 && base + 64 < n) continue;
             }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            const int take = n_emit < 64 ? n_emit : 64;
-            if (lane < take) shade_emission<KIND == HK_MAT_MATTE, SIMPLE, LEAN>(st, g, ones, sc, T, elist[lane], n_lnodes, depth, seg);
-            nl_flush();
-            const int rest = n_emit - take;
-            const uint32_t moved = lane < rest ? elist[64 + lane] : 0u;
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            if (lane < rest) elist[lane] = moved;
-            n_emit = rest;
+            emit_pass(n_emit < 64 ? n_emit : 64);
         }
+    }
+    // LEAN fetch-ahead: this wave's 64 entries of every staging part; the entry of chunk 1 is requested before chunk 0 starts
+    const bool prefetch = LEAN && stage.entry != nullptr;
+    const int wave0 = LEAN ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u)) : 0;
+    if constexpr (LEAN) {
+        if (prefetch && 64 + lane < n) lds_fetch4(&queue[64 + lane], stage.entry + 256 + wave0);
     }
     for (int base = 0; base < n; base += 64) {
         int i = base + lane;
         bool active = i < n;
+        if constexpr (LEAN) {   // the entry of chunk k + 2 (never one at or past n): its address depends on nothing
+            if (prefetch && i + 128 < n) lds_fetch4(&queue[i + 128], stage.entry + ((base >> 6) & 1) * 256 + wave0);
+        }
+        const bool staged = prefetch && base > 0;   // this chunk's hit, ray_d and meta word were requested from the middle of the chunk before
         uint32_t slot = active ? queue[i] : 0u;   // generation index of the path (the kind queue is a sorted subset of the segment)
+        {   // the entry's flag: an emissive hit waits in the list for the dense K8 pass (at most 63 waiting + 64 new of its 128 words)
+            const bool em = !prescan && (slot & HK_MATQ_EMISSIVE) != 0u;
+            slot &= ~HK_MATQ_EMISSIVE;
+            const unsigned long long m = __ballot(em);
+            if (m != 0ull) {
+                if (em) elist[n_emit + __popcll(m & ((1ull << lane) - 1ull))] = slot;
+                n_emit += __popcll(m);
+                if (n_emit >= 64) emit_pass(64);
+            }
+        }
         bool push_shadow = false, push_ray = false;
         // state shared by the two halves of the vertex (NEE, then BSDF sampling): loaded once
         float4 H = make_float4(0, 0, 0, 0);
@@ -2794,17 +2851,25 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
         if constexpr (LEAN) nv_wave += (unsigned)(n - base < 64 ? n - base : 64);   // (wave-uniform: a scalar register)
         if (active) {
             if constexpr (!LEAN) ++n_vertices;
-            H = stream_ld(&st.hit[slot]);
-            float4 O = ld_ray_o(st, g, slot, depth, seg), D = stream_ld(&g.ray_d[slot]);
+            float4 D;
+            uint32_t meta_w = 0;   // LEAN: the record's 32-bit meta word (path slot, specular and any-non-specular bits)
+            if (LEAN && staged) {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the staged records have landed
+                const int t = (int)threadIdx.x;
+                H = stage.hit[t], D = stage.ray_d[t], meta_w = stage.meta[t];
+            } else {
+                H = stream_ld(&st.hit[slot]);
+                D = stream_ld(&g.ray_d[slot]);
+                if constexpr (LEAN) meta_w = reinterpret_cast<const uint32_t*>(g.meta)[slot];
+            }
+            float4 O = ld_ray_o(st, g, slot, depth, seg);
             v3 ro = mk3(O.x, O.y, O.z), rd = mk3(D.x, D.y, D.z);
             float t_hit = H.x;
             int prim = __float_as_int(H.y);
             sf = surface_at(sc, prim, H.z, H.w, ro, rd, t_hit);
             wo = -rd;
             meta = tri_meta(sc, prim);
-            uint32_t meta_w = 0;   // LEAN: the record's 32-bit meta word (path slot, specular and any-non-specular bits)
             if constexpr (LEAN) {
-                meta_w = reinterpret_cast<const uint32_t*>(g.meta)[slot];
                 pslot = meta_w & 0x3fffffffu;
                 pdepth = depth;   // (what ld_meta returns for a 32-bit word: every path of the depth-d queues is at depth d)
                 any_non_specular = (meta_w >> 31) != 0u;
@@ -2890,6 +2955,14 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
                 sp[6 * 256] = kd_matte.x, sp[7 * 256] = kd_matte.y, sp[8 * 256] = kd_matte.z, sp[9 * 256] = kd_matte.w;
                 sp[10 * 256] = beta.x, sp[11 * 256] = beta.y, sp[12 * 256] = beta.z, sp[13 * 256] = beta.w;
                 sp[14 * 256] = __uint_as_float(meta_w);
+                // the registers are at their lowest here: the next chunk's entry (requested a chunk ago) names the records to stage
+                if (prefetch && i + 64 < n) {
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the entry has landed
+                    const uint32_t ns = stage.entry[(((base >> 6) + 1) & 1) * 256 + (int)threadIdx.x] & ~HK_MATQ_EMISSIVE;
+                    lds_fetch16(&st.hit[ns], stage.hit + wave0);
+                    lds_fetch16(&g.ray_d[ns], stage.ray_d + wave0);
+                    lds_fetch4(reinterpret_cast<const uint32_t*>(g.meta) + ns, stage.meta + wave0);
+                }
             }
             // ---- K9: next-event estimation through the light BVH ----
             if (sc.n_lights > 0) {
@@ -3060,6 +3133,7 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
             }
         }
     }
+    if (n_emit > 0) emit_pass(n_emit);   // the flagged entries still waiting (fewer than 64)
     if (lane == 0) {
         *count_ptr(st, depth, Q_SHADOW, gw) = q_shadow.count;
         *count_ptr(st, depth + 1, Q_RAY, gw) = q_next.count;
@@ -3079,8 +3153,15 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256, 256), amdgpu_wav
     SegTickets src = seg_open(st, ticket_ptr(st, depth, TK_SHADE0 + KIND), st.dynamic_segments != 0, depth, Q_MAT0 + KIND);
     if constexpr (LEAN) {
         src.pos = __builtin_amdgcn_readfirstlane(src.pos), src.k0 = __builtin_amdgcn_readfirstlane(src.k0);   // (wave-uniform: the wave's index)
-        __shared__ float stash[HK_SHADE_STASH * 256];   // five blocks per CU: 5 x (2 KB + 16 KB) of the CU's 160 KB
-        shade_body<KIND, SIMPLE, FT, PRE, true>(st, sc, T, fr, sob, depth, first_kind, stats, src, emit_list + (threadIdx.x >> 6) * 128, stash);
+        __shared__ float stash[HK_SHADE_STASH * 256];   // five blocks per CU: 5 x (2 KB + 16 KB + 11 KB) of the CU's 160 KB
+        // the staging area of the fetch-ahead: objects of their own, so that the compiler can tell its reads from the stash's
+        __shared__ uint32_t stage_entry[2 * 256];
+        __shared__ float4 stage_hit[256];
+        __shared__ float4 stage_ray_d[256];
+        __shared__ uint32_t stage_meta[256];
+        ShadeStage stage{};
+        if (st.shade_prefetch) stage.entry = stage_entry, stage.hit = stage_hit, stage.ray_d = stage_ray_d, stage.meta = stage_meta;
+        shade_body<KIND, SIMPLE, FT, PRE, true>(st, sc, T, fr, sob, depth, first_kind, stats, src, emit_list + (threadIdx.x >> 6) * 128, stash, stage);
     } else
         shade_body<KIND, SIMPLE, FT, PRE>(st, sc, T, fr, sob, depth, first_kind, stats, src, emit_list + (threadIdx.x >> 6) * 128);
 }
@@ -3257,6 +3338,7 @@ __device__ __forceinline__ void trace_shadow_body(const DPathState& st, const DS
         const unsigned long long run_m = __ballot(state == LR_ACTIVE && r.cur != DONE);
         if (run_m == 0ull || (64 - __popcll(run_m) >= HK_TRACE_MIN_IDLE && (cur_ray < n_ray || cur_sh < n_sh))) {
             int kind = -1;
+            uint32_t eflag = 0u;   // HK_MATQ_EMISSIVE when the hit triangle carries an area light: travels in the kind-queue entry
             if (state == LR_ACTIVE && r.cur == DONE) {
                 if (r.any) {   // a shadow ray: unoccluded, it delivers its contribution
                     if (r.best.prim < 0) {
@@ -3271,6 +3353,7 @@ __device__ __forceinline__ void trace_shadow_body(const DPathState& st, const DS
                 else {
                     ++n_hits;
                     const DTriMeta hm = sc.meta[r.best.prim];
+                    eflag = hm.arealight > 0 ? HK_MATQ_EMISSIVE : 0u;
                     int mat = sc.mis[hm.mi].material;
                     if (sc.materials[mat].kind == HK_MAT_MIX) {
                         float w = 1.0f - r.best.u - r.best.v;
@@ -3293,7 +3376,7 @@ __device__ __forceinline__ void trace_shadow_body(const DPathState& st, const DS
                 int cnt = 0;
 #pragma unroll
                 for (int kk = 0; kk < HK_MAX_KINDS; ++kk) cnt = (kk == k) ? kind_count[kk] : cnt;
-                if (mine) stream_st(&st.mat_q[((size_t)k * st.n_waves + gw) * st.wave_cap + cnt + __popcll(m & lt_mask)], slot);
+                if (mine) stream_st(&st.mat_q[((size_t)k * st.n_waves + gw) * st.wave_cap + cnt + __popcll(m & lt_mask)], slot | eflag);
                 int add = __popcll(m);
 #pragma unroll
                 for (int kk = 0; kk < HK_MAX_KINDS; ++kk) kind_count[kk] += (kk == k) ? add : 0;

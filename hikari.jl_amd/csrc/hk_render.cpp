@@ -269,6 +269,9 @@ int ensure_state(hk_integrator* I, int capacity, const PassTraits& t, hipStream_
     // lean generation records of the same scenes (HK_LEAN_RECORDS=0: 8-byte meta words, depth-0 origins stored; A/B switch, films bit-identical)
     I->st.meta32 = (lean && hk::knob_on("HK_LEAN_RECORDS")) ? 1 : 0;
     I->st.const_origin = 0;   // (per call: render_tile_now knows the camera)
+    // HK_SHADE_PRESCAN=1: k_shade looks a segment's emissive hits up in mat_id before its first vertex, as it did before the flag travelled in the kind-queue entry (A/B switch, films bit-identical)
+    I->st.shade_prescan = hk::knob_int("HK_SHADE_PRESCAN", 0) != 0 ? 1 : 0;
+    I->st.shade_prefetch = hk::knob_on("HK_SHADE_PREFETCH") ? 1 : 0;   // 0: the LEAN k_shade loads every chunk's records directly (A/B switch, films bit-identical)
     I->st.ticket_share = hk::knob_int("HK_TICKET_SHARE", 1) ? 1 : 0;
     {   // a SMALL pass (at most 16 chunks for each of 4 waves per CU: a one-sample call at 800^2) hands segment g to wave g of every launch
         // (static stride where a grid is smaller): the 17 k_segment_lists launches of a call and the ticket round trips go, and the segment
@@ -314,6 +317,8 @@ int ensure_state(hk_integrator* I, int capacity, const PassTraits& t, hipStream_
     s.capacity = capacity;
     s.n_waves = W;
     s.wave_cap = ((chunks + W - 1) / W) * 64;
+    // a generation index is below W * wave_cap; the kind queues keep the emissive flag in an entry's top bit (HK_MATQ_EMISSIVE)
+    if ((size_t)W * (size_t)s.wave_cap > 0x7fffffffu) return fail(HK_ERR_INVALID, "pass too large");
     if (hk::knob_on("HK_STATE_SLAB")) {   // (0: one allocation per array, nothing cached)
         // the camera generation is part of the slab when the slab still fits with it (the pass is never made smaller for its sake):
         // measured with it first, and once more without when the memory is not there

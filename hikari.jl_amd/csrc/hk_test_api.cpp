@@ -192,3 +192,28 @@ extern "C" int32_t hk_test_medium_bricks(hk_scene* s, int32_t idx, int32_t* dims
     HIP_TRY(hipMemcpy(out, d.nv_bricks, (size_t)d.nvb_dim[0] * d.nvb_dim[1] * d.nvb_dim[2] * 729 * sizeof(float), hipMemcpyDeviceToHost));
     return HK_OK;
 }
+
+extern "C" int32_t hk_test_queue_counts(hk_integrator* I, int32_t depth, int32_t kind, int32_t* n_segments, int32_t* counts, int32_t* flagged) {
+    if (!I || !n_segments) return fail(HK_ERR_INVALID, "hk_test_queue_counts: null argument");
+    if (kind < 0 || kind >= HK_MAX_KINDS || depth < 0 || depth >= I->st_depth + 2) return fail(HK_ERR_INVALID, "hk_test_queue_counts: kind or depth out of range");
+    if (!I->st.counters) return fail(HK_ERR_INVALID, "hk_test_queue_counts: no pass has been rendered");
+    *n_segments = I->st.n_waves;
+    if (!counts) return HK_OK;
+    hk_ctx* c = I->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    KnobScope knobs(&c->knobs);
+    if (int e = join_lanes(c)) return e;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(counts, I->st.counters + (size_t)(depth * Q_COUNT + Q_MAT0 + kind) * I->st.n_waves, (size_t)I->st.n_waves * sizeof(int), hipMemcpyDeviceToHost));
+    if (!flagged) return HK_OK;
+    // the entries themselves (the kind's queue is overwritten by every bounce: they are those of the bounce traced last)
+    const size_t Q = (size_t)I->st.n_waves * I->st.wave_cap;
+    std::vector<uint32_t> q(Q);
+    HIP_TRY(hipMemcpy(q.data(), I->st.mat_q + (size_t)kind * Q, Q * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (int w = 0; w < I->st.n_waves; ++w) {
+        int n = 0;
+        for (int i = 0; i < counts[w] && i < I->st.wave_cap; ++i) n += (q[(size_t)w * I->st.wave_cap + i] & HK_MATQ_EMISSIVE) != 0u;
+        flagged[w] = n;
+    }
+    return HK_OK;
+}

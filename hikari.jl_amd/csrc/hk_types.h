@@ -50,6 +50,7 @@ struct DNode {
 };
 
 #define HK_MAT_EMISSIVE_BIT 0x40000000   // DPathState::mat_id: the hit triangle carries an area light (set by the trace kernels)
+#define HK_MATQ_EMISSIVE 0x80000000u     // DPathState::mat_q: the same flag in the top bit of the kind-queue entry (a generation index is below 2^31: ensure_state)
 #define HK_TRI_OPAQUE 1u  // e1.w bit: surface is neither a medium transition nor alpha-tested
 
 // sigmoid-polynomial spectrum with optional scale (c0,c1,c2,scale)
@@ -418,7 +419,7 @@ struct DPathState {
     uint32_t* medium_q;    // rays that travel inside a medium (delta tracking before their surface hit is processed)
     uint32_t* scatter_q;   // paths that scattered inside a medium at this depth (K5/K6 input)
     int* initial_medium;   // camera medium detected on the device (K14)
-    uint32_t* mat_q;       // HK_MAX_KINDS * W * wave_cap
+    uint32_t* mat_q;       // HK_MAX_KINDS * W * wave_cap; an entry is the generation index | HK_MATQ_EMISSIVE when the hit triangle carries an area light (every reader masks it)
     int* counters;         // [(max_depth + 2) * Q_COUNT][W] per-wave queue sizes
     int* tickets;          // [ticket_rows * HK_TICKET_COLS][HK_TICKET_WAYS * HK_TICKET_STRIDE] segment tickets (dynamic segment -> wave assignment), zeroed per pass
     int ticket_rows;       // max_depth + 2
@@ -446,6 +447,8 @@ struct DPathState {
     // stores zeros to the L entries it has read (what k_camera's L = 0 store did for the next pass).
     DPathGen gen_cam;
     int view_cache;
+    int shade_prescan;     // 1 (HK_SHADE_PRESCAN=1; A/B switch, films bit-identical): k_shade finds a segment's emissive hits by a scan of mat_id before its first vertex instead of by the flag in the queue entry
+    int shade_prefetch;    // 1 (HK_SHADE_PREFETCH=0: off; A/B switch, films bit-identical): the LEAN k_shade stages the next chunk's hit, ray_d and meta word in LDS by global->LDS loads
 };
 
 struct DStats {

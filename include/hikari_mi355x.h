@@ -695,6 +695,12 @@ int32_t hk_scene_medium_copy(hk_scene* scene, int32_t idx, int32_t* n_cells, flo
 /* The halo bricks of NanoVDB medium `idx` as the device holds them: dims[3] = the block table's extent (all 0 when the medium has no
    bricks), out (NULL: only the extent) = dims[0]*dims[1]*dims[2] bricks of 729 floats, block (bx, by, bz) at bz + dims[2]*(by + dims[1]*bx). */
 int32_t hk_test_medium_bricks(hk_scene* scene, int32_t idx, int32_t* dims, float* out);
+/* The sizes the shading queue of material kind `kind` (HK_MAT_*) had at bounce `depth` in the integrator's last pass, one per wave
+   segment of the path state: *n_segments = the number of segments, counts (NULL: only *n_segments) = that many entry counts — what
+   one wave of k_shade walked in 64-entry chunks.  flagged (NULL: not wanted; needs counts): per segment, how many of those entries carry
+   the emissive flag — read from the queue itself, which every bounce overwrites, so `depth` must be the bounce traced last (a pass of
+   max_depth 1: depth 0).  Staged passes only (a pass rendered in one fused launch leaves no counts); waits for the context's stream. */
+int32_t hk_test_queue_counts(hk_integrator* integrator, int32_t depth, int32_t kind, int32_t* n_segments, int32_t* counts, int32_t* flagged);
 
 #ifdef __cplusplus
 }
