@@ -291,6 +291,9 @@ struct hk_scene {
         DevBuf *nvdb = nullptr, *blocks = nullptr, *bricks = nullptr;   // NanoVDB: these grow with the tree (bricks: empty while they do not fit HK_NVDB_DENSE_MB)
     };
     std::vector<Medium> h_media;
+    // hk_scene_update_medium_dense: the field as uploaded (a host source only) and the build's working set — control record, flags,
+    // slots, lists and tile sums of the three levels; both grow with the largest field
+    DevBuf dense_field, dense_work;
     // the arrays the records above point into (texels, spectra, envmap tables, medium grids): freed with the scene, after the staging
     // events below have been waited for (the destructor's body runs before the members go)
     std::vector<std::unique_ptr<DevBuf>> owned;
@@ -321,6 +324,9 @@ struct NvdbPlan {   // what the device holds of a NanoVDB tree besides its bytes
     void fill(DMedium& o) const;
 };
 int plan_nanovdb(const hk_medium& m, NvdbPlan& p);   // HK_OK, or the refusal of the tree (fail())
+// the part of it that follows from the extent (p.nvb_min / p.nvb_dim as scanned) and the size alone: the table's dimensions and limits,
+// the brick budget.  hk_scene_update_medium_dense, whose table is built on the device, plans with this.
+int plan_nanovdb_shape(long long nvdb_size, NvdbPlan& p);
 struct MediaClasses {
     int media_mask = 0, all_grey = 0, grey_pool = 0, grey_bricks = 0;
 };

@@ -5575,5 +5575,6 @@ __global__ void __launch_bounds__(256) k_nvdb_bricks(DMedium m, unsigned long lo
     }
 }
 
+#include "hk_nvdb_build.h"
 #include "hk_launch_impl.h"
 #include "hk_test_kernels.h"

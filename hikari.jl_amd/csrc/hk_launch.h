@@ -64,6 +64,10 @@ void launch_envmap_tables(hipStream_t s, const DEnvMap& e, DEnvMap* record);
 void launch_majorant_grid(hipStream_t s, const DMedium& m);
 void launch_majorant_nanovdb(hipStream_t s, const DMedium& m, const DIndexBox& index_bbox);
 void launch_nvdb_bricks(hipStream_t s, const DMedium& m, size_t n_blocks);
+// hk_scene_update_medium_dense (hk_nvdb_build.h): the flags, node numbering and counts of the tree of a dense field into D.lev / D.ctl;
+// then, once the host has read D.ctl and sized the tree, the tree's bytes and its block table
+void launch_dense_count(hipStream_t s, const DDense& D);
+void launch_dense_emit(hipStream_t s, const DDense& D, const uint32_t count[3], size_t n_bytes);
 
 // ---- sub-kernel entry points of the parity tests (hk_test_kernels.h) ----
 void launch_test_trace(hipStream_t s, const DScene& sc, int n, const float* o, const float* d, const float* tmax, float* t, int* prim, float* uv);

@@ -483,4 +483,26 @@ void launch_nvdb_bricks(hipStream_t s, const DMedium& m, size_t n_blocks) {
     hipLaunchKernelGGL(k_nvdb_bricks, dim3((unsigned)std::min<unsigned long long>((n_out + 255) / 256, 1u << 20)), dim3(256), 0, s, m, n_out, const_cast<float*>(m.nv_bricks));
 }
 
+// hk_scene_update_medium_dense, before its one wait: flags of the three levels, their prefix sums and lists, and D.ctl (zeroed here)
+void launch_dense_count(hipStream_t s, const DDense& D) {
+    (void)hipMemsetAsync(D.ctl, 0, sizeof(DDenseCtl), s);
+    const int f = D.fast, a = f == 0 ? 1 : 0, b = f == 0 ? 2 : 1;
+    const unsigned n_chunk = (unsigned)(((long long)D.res[f] + 63) / 64);   // (n_chunk * blocks of the two other axes <= the field's blocks <= 2^27)
+    hipLaunchKernelGGL(k_dense_flags, dim3(n_chunk * (unsigned)D.lev[0].dim[a] * (unsigned)D.lev[0].dim[b]), dim3(64), 0, s, D, n_chunk);
+    for (int to = 1; to <= 2; ++to) hipLaunchKernelGGL(k_dense_group, dim3(std::min(D.lev[to].n, 1u << 16)), dim3(64), 0, s, D, to);
+    const unsigned tiles = D.lev[0].tiles + D.lev[1].tiles + D.lev[2].tiles;
+    hipLaunchKernelGGL(k_dense_tile_sums, dim3(tiles), dim3(256), 0, s, D);
+    hipLaunchKernelGGL(k_dense_scan_sums, dim3(3), dim3(256), 0, s, D);
+    hipLaunchKernelGGL(k_dense_slots, dim3(tiles), dim3(256), 0, s, D);
+}
+// ... and after it: the tree of n_bytes (zeroed here; count[] as read back) and the block table of the extent in D
+void launch_dense_emit(hipStream_t s, const DDense& D, const uint32_t count[3], size_t n_bytes) {
+    (void)hipMemsetAsync(D.tree, 0, n_bytes, s);
+    if (count[0]) hipLaunchKernelGGL(k_dense_leaves, dim3(count[0]), dim3(64), 0, s, D);
+    if (count[1]) hipLaunchKernelGGL(k_dense_nodes<1>, dim3(count[1]), dim3(256), 0, s, D);
+    if (count[2]) hipLaunchKernelGGL(k_dense_nodes<2>, dim3(count[2]), dim3(256), 0, s, D);
+    const unsigned long long n = (unsigned long long)D.nvb_dim[0] * D.nvb_dim[1] * D.nvb_dim[2];
+    hipLaunchKernelGGL(k_dense_table, dim3((unsigned)std::min<unsigned long long>((n + 255) / 256, 1u << 20)), dim3(256), 0, s, D, n);
+}
+
 }  // namespace hk

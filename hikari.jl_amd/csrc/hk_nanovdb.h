@@ -7,6 +7,26 @@
 
 namespace hknv {
 
+// The layout of the node-only buffer [Root | Upper nodes | Lower nodes | Leaf nodes] (nanovdb.jl:153-191; media.py carries the same
+// numbers for the host builder), 0-based byte positions inside a node.  The device tree builder (hk_nvdb_build.h) writes by these.
+enum : long long {
+    ROOT_HEADER = 64,        // index bbox min / max (6 x int32), table size (uint32 at 24), background (float at 28)
+    ROOT_TILE = 32,          // key (uint64), child offset from the root (int64 at 8), state (uint32 at 16), value (float at 20)
+    UPPER_VALUEMASK = 32,    // bbox min / max (6 x int32) come first in an upper and a lower node
+    UPPER_CHILDMASK = 4128,
+    UPPER_TABLE = 8256,      // 32768 entries of 8 bytes: child offset from the node (int64), or a tile value
+    UPPER_SIZE = UPPER_TABLE + 32768 * 8,
+    LOWER_VALUEMASK = 32,
+    LOWER_CHILDMASK = 544,
+    LOWER_TABLE = 1088,      // 4096 entries of 8 bytes
+    LOWER_SIZE = LOWER_TABLE + 4096 * 8,
+    LEAF_FLAGS = 12,         // origin (3 x int32) first; then the three bytes 7, 7, 7 (bbox extent of a full leaf)
+    LEAF_MASK = 16,          // 512 bits, bit (lx << 6) | (ly << 3) | lz
+    LEAF_MIN = 80,           // minimum, then maximum, of the 512 values
+    LEAF_VALUES = 96,        // 512 floats, lz fastest
+    LEAF_SIZE = LEAF_VALUES + 512 * 4,
+};
+
 HK_HD float f32(const unsigned char* b, long long off1) { return *reinterpret_cast<const float*>(b + (((off1 - 1) >> 2) << 2)); }
 HK_HD long long i64(const unsigned char* b, long long off1) { return *reinterpret_cast<const long long*>(b + (((off1 - 1) >> 3) << 3)); }
 HK_HD bool mask(const unsigned char* b, long long mask_off1, int n) { return ((b[mask_off1 - 1 + (n >> 3)] >> (n & 7)) & 1) != 0; }

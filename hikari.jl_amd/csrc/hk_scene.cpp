@@ -553,24 +553,28 @@ std::vector<float> nvdb_dense_bricks(const hk_medium& m, const std::vector<uint2
 }
 }  // namespace
 // What the device holds of a NanoVDB tree besides its bytes: extent and background of the block table, the table, and whether the halo
-// bricks fit HK_NVDB_DENSE_MB.  Every refusal of a tree is here, for hk_scene_create and hk_scene_update_medium alike.
-int plan_nanovdb(const hk_medium& m, NvdbPlan& p) {
-    if (!m.nvdb_bytes || m.nvdb_size <= 0) return fail(HK_ERR_INVALID, "NanoVDB medium without tree bytes");
-    if (!nvdb_block_extent(m, p.background, p.nvb_min, p.nvb_dim)) return fail(HK_ERR_UNSUPPORTED, "NanoVDB grid with a non-background root tile (4096^3 constant region) is not supported");
-    long long dim[3];
+// bricks fit HK_NVDB_DENSE_MB.  Every refusal of a tree is here, for hk_scene_create and hk_scene_update_medium alike; the limits and the
+// budget, which follow from the extent alone, also for hk_scene_update_medium_dense (plan_nanovdb_shape).
+int plan_nanovdb_shape(long long nvdb_size, NvdbPlan& p) {
     p.total = 1;
     for (int k = 0; k < 3; ++k) {
-        dim[k] = p.nvb_dim[k] < 3 ? 3 : p.nvb_dim[k];
-        p.total *= dim[k];
+        if (p.nvb_dim[k] < 3) p.nvb_dim[k] = 3;
+        p.total *= (long long)p.nvb_dim[k];
     }
-    if (p.total > (1ll << 27) || m.nvdb_size >= (1ll << 32)) {
+    if (p.total > (1ll << 27) || nvdb_size >= (1ll << 32)) {
         return fail(HK_ERR_UNSUPPORTED, "NanoVDB grid too large for the device block table (index bbox > 2^27 blocks or buffer >= 4 GiB)");
     }
-    if (!nvdb_block_table(m, p.nvb_min, dim, p.background, p.table)) return fail(HK_ERR_INVALID, "NanoVDB block table: non-background data on the margin (corrupt tree?)");
-    for (int k = 0; k < 3; ++k) p.nvb_dim[k] = (int)dim[k];
     size_t budget_mb = 4096;
     if (const char* e = hk::knob("HK_NVDB_DENSE_MB")) budget_mb = (size_t)std::atol(e);
     p.bricks = (size_t)p.total * 729 * sizeof(float) <= budget_mb * (size_t)(1 << 20);
+    return HK_OK;
+}
+int plan_nanovdb(const hk_medium& m, NvdbPlan& p) {
+    if (!m.nvdb_bytes || m.nvdb_size <= 0) return fail(HK_ERR_INVALID, "NanoVDB medium without tree bytes");
+    if (!nvdb_block_extent(m, p.background, p.nvb_min, p.nvb_dim)) return fail(HK_ERR_UNSUPPORTED, "NanoVDB grid with a non-background root tile (4096^3 constant region) is not supported");
+    if (int e = plan_nanovdb_shape(m.nvdb_size, p)) return e;
+    const long long dim[3] = {p.nvb_dim[0], p.nvb_dim[1], p.nvb_dim[2]};
+    if (!nvdb_block_table(m, p.nvb_min, dim, p.background, p.table)) return fail(HK_ERR_INVALID, "NanoVDB block table: non-background data on the margin (corrupt tree?)");
     return HK_OK;
 }
 void NvdbPlan::fill(DMedium& o) const {

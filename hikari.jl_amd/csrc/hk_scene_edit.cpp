@@ -1,14 +1,15 @@
 // hk_scene_edit.cpp — in-place scene edits: hk_scene_set_transform (device transform + BVH refit), hk_scene_set_vertices (new base
 // geometry of a triangle range in one device pass + BVH refit), hk_scene_update_materials, hk_scene_update_lights (records + host
 // rebuild of the light BVH), hk_scene_update_envmap (rotation, texels + device table build) and hk_scene_update_medium (record, volume
-// data + device build of majorant grid, zero-cell mask and NanoVDB bricks) and hk_scene_rebuild_bvh (a new BVH topology built on the
-// device); hk_scene_bvh_cost / hk_scene_bvh_copy / hk_scene_bvh_leaves read the tree back.
+// data + device build of majorant grid, zero-cell mask and NanoVDB bricks), hk_scene_update_medium_dense (the NanoVDB tree of a dense
+// field and its block table built on the device as well) and hk_scene_rebuild_bvh (a new BVH topology built on the
+// device); hk_scene_bvh_cost / hk_scene_bvh_copy / hk_scene_bvh_leaves read the tree back, hk_scene_medium_tree_copy a NanoVDB tree.
 #include "hk_host.h"
 #include "hk_bvh_decide.h"
 
 // ---- in-place scene edits -----------------------------------------------------------------------------------------------------
-// No entry point but hk_scene_rebuild_bvh waits for the device: the noted calls are rendered first (against the scene as it was), the
-// lanes are joined, and the work is enqueued on the context's stream behind everything already there.  Every argument is checked
+// Only hk_scene_rebuild_bvh and hk_scene_update_medium_dense wait for the device, once each and for a small record.  For every
+// entry point the noted calls are rendered first (against the scene as it was), the lanes are joined, and the work is enqueued on the context's stream behind everything already there.  Every argument is checked
 // before anything changes.  (hk_scene_rebuild_bvh waits once, for the size of the tree it built; it is also the one edit that changes
 // bvh_depth and n_nodes — what follows from that is argued at its entry point.)
 // Caches keyed by the scene that an edit must not invalidate, and why it does not: DScene::all_opaque and the HK_TRI_OPAQUE bits (opacity
@@ -352,6 +353,36 @@ void swap_buffers(DevBuf& a, DevBuf& b) {
     std::swap(a.slab_dev, b.slab_dev);
 }
 size_t staged(size_t bytes) { return (bytes + 255) & ~(size_t)255; }   // every block of a staging buffer starts on a 256-byte boundary
+// the classes of the scene with `o` as medium idx, by hk_scene_create's code: empty, or the refusal of an edit that would change one
+std::string media_class_refusal(const hk_scene* s, int idx, const DMedium& o) {
+    const int NM = (int)s->h_media.size();
+    std::vector<DMedium> all(NM);
+    for (int i = 0; i < NM; ++i) all[i] = s->h_media[i].d;
+    all[idx] = o;
+    const MediaClasses mc = classify_media(all, NM);
+    const DScene& D = s->d;
+    if (mc.media_mask == D.media_mask && mc.all_grey == D.all_grey && mc.grey_pool == D.grey_pool && mc.grey_bricks == D.grey_bricks) return std::string();
+    return mc.grey_bricks != D.grey_bricks ? "the class of the scene's media would change (halo bricks against HK_NVDB_DENSE_MB: grey_bricks)"
+                                           : "the class of the scene's media would change (a grey medium turning coloured or the reverse: all_grey / grey_pool)";
+}
+// a tree that needs more than the NanoVDB buffers hold (tree bytes, block table, bricks) gets new ones: all are allocated before any is
+// exchanged, and the stream is waited for before the old ones go (passes already enqueued read them)
+int fit_nanovdb_buffers(hk_ctx* c, hk_scene::Medium& hm, const size_t need[3]) {
+    DevBuf fresh[3];
+    DevBuf* const have[3] = {hm.nvdb, hm.blocks, hm.bricks};
+    bool grow = false;
+    for (int k = 0; k < 3; ++k)
+        if (have[k]->bytes < need[k]) {
+            HIP_TRY(fresh[k].alloc(need[k]));
+            grow = true;
+        }
+    if (grow) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (int k = 0; k < 3; ++k)
+            if (fresh[k].p) swap_buffers(*have[k], fresh[k]);
+    }
+    return HK_OK;
+}
 }  // namespace
 
 // Medium `idx` becomes *mp.  What this leaves valid, and why: the view cache (hk_render.cpp) is off in scenes with media, so no camera
@@ -385,15 +416,9 @@ extern "C" int32_t hk_scene_update_medium(hk_scene* s, int32_t idx, const hk_med
         plan.fill(o);
         o.nv_bricks = plan.bricks ? reinterpret_cast<const float*>(&plan) : nullptr;   // (for the class check; the buffer's address follows)
     }
-    {   // the classes of the edited scene, by hk_scene_create's code
-        std::vector<DMedium> all(NM);
-        for (int i = 0; i < NM; ++i) all[i] = s->h_media[i].d;
-        all[idx] = o;
-        const MediaClasses mc = classify_media(all, NM);
-        const DScene& D = s->d;
-        if (mc.media_mask != D.media_mask || mc.all_grey != D.all_grey || mc.grey_pool != D.grey_pool || mc.grey_bricks != D.grey_bricks)
-            return fail(HK_ERR_INVALID, at + (mc.grey_bricks != D.grey_bricks ? "the class of the scene's media would change (halo bricks against HK_NVDB_DENSE_MB: grey_bricks)"
-                                                                              : "the class of the scene's media would change (a grey medium turning coloured or the reverse: all_grey / grey_pool)"));
+    {
+        std::string bad = media_class_refusal(s, idx, o);
+        if (!bad.empty()) return fail(HK_ERR_INVALID, at + bad);
     }
     // one staging block: the record, then the data that crosses to the device (voxel grids, or tree bytes and block table)
     const size_t nvox = (size_t)m.res[0] * m.res[1] * m.res[2];
@@ -408,22 +433,8 @@ extern "C" int32_t hk_scene_update_medium(hk_scene* s, int32_t idx, const hk_med
     if (int e = acquire_staging(s, total, st)) return e;
     if (int e = join_lanes(c)) return e;   // noted calls render the old medium; the lanes finish before the stream rewrites it
     if (m.kind == HK_MEDIUM_NANOVDB) {
-        // a tree that needs more than the buffers hold gets new ones: all are allocated before any is exchanged, and the stream is
-        // waited for before the old ones go (passes already enqueued read them)
-        DevBuf fresh[3];
-        DevBuf* const have[3] = {hm.nvdb, hm.blocks, hm.bricks};
         const size_t need[3] = {b_tree, b_table, b_bricks};
-        bool grow = false;
-        for (int k = 0; k < 3; ++k)
-            if (have[k]->bytes < need[k]) {
-                HIP_TRY(fresh[k].alloc(need[k]));
-                grow = true;
-            }
-        if (grow) {
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            for (int k = 0; k < 3; ++k)
-                if (fresh[k].p) swap_buffers(*have[k], fresh[k]);
-        }
+        if (int e = fit_nanovdb_buffers(c, hm, need)) return e;
         o.nvdb = hm.nvdb->as<unsigned char>();
         o.nv_blocks = hm.blocks->as<uint2>();
         o.nv_bricks = plan.bricks ? hm.bricks->as<float>() : nullptr;
@@ -458,6 +469,169 @@ extern "C" int32_t hk_scene_update_medium(hk_scene* s, int32_t idx, const hk_med
     HIP_TRY(hipEventRecord(st->ev, c->stream));
     hm.rec = m;
     hm.d = o;
+    return HK_OK;
+}
+
+// NanoVDB medium `idx` becomes the tree of a dense field, built on the device (hk_nvdb_build.h).  The scene is left as
+// hk_scene_update_medium leaves it for the host-built tree of the same field, and what that call leaves valid stays valid for the same
+// reasons.  Everything before the one wait writes the scene's working buffers only; every refusal comes before the first write to a
+// buffer a record points to, so a refused call leaves the scene as it was.  hk_scene::Medium::rec gets no pointer to tree bytes: there
+// are none on the host (its pointers are never followed — check_medium_update and hk_scene_medium_tree_copy read its plain fields).
+extern "C" int32_t hk_scene_update_medium_dense(hk_scene* s, int32_t idx, const hk_medium* mp, const hk_dense_field* fp) {
+    if (!s || !mp || !fp || !fp->data) return fail(HK_ERR_INVALID, "hk_scene_update_medium_dense: null argument");
+    const int NM = (int)s->h_media.size();
+    if (idx < 0 || idx >= NM) return fail(HK_ERR_INVALID, "hk_scene_update_medium_dense: medium index out of range");
+    hk_scene::Medium& hm = s->h_media[idx];
+    const hk_dense_field& F = *fp;
+    const std::string at = "hk_scene_update_medium_dense: medium " + std::to_string(idx) + ": ";
+    if (hm.rec.kind != HK_MEDIUM_NANOVDB) return fail(HK_ERR_INVALID, at + "not a NanoVDB medium");
+    if (F.res[0] < 1 || F.res[1] < 1 || F.res[2] < 1) return fail(HK_ERR_INVALID, at + "res below 1");
+    if (F.layout != HK_DENSE_X_FASTEST && F.layout != HK_DENSE_Z_FASTEST) return fail(HK_ERR_INVALID, at + "unknown layout");
+    hk_medium m = *mp;   // the record hk_scene_update_medium would be given: the map as build_nanovdb_from_dense derives it, in binary32
+    std::memset(m.inv_mat, 0, sizeof m.inv_mat);
+    for (int k = 0; k < 3; ++k) {
+        const float d = (m.bounds_max[k] - m.bounds_min[k]) / (float)F.res[k];
+        m.inv_mat[4 * k] = 1.0f / d;
+        m.vec[k] = m.bounds_min[k] + d / 2.0f;
+    }
+    m.nvdb_bytes = nullptr, m.majorant = nullptr, m.max_density = 0.0f;
+    {
+        std::string bad = check_medium_update(hm.rec, m);
+        if (!bad.empty()) return fail(HK_ERR_INVALID, at + bad);
+    }
+    // the three levels over the field's extent: 8^3 blocks, lower nodes of 16^3 blocks, upper nodes of 32^3 lower nodes
+    DDense D{};
+    long long n_lev[3];
+    for (int k = 0; k < 3; ++k) {
+        D.res[k] = F.res[k];
+        D.lev[0].dim[k] = (int)(((long long)F.res[k] + 7) / 8);
+        D.lev[1].dim[k] = (D.lev[0].dim[k] + 15) / 16;
+        D.lev[2].dim[k] = (D.lev[1].dim[k] + 31) / 32;
+    }
+    for (int L = 0; L < 3; ++L) n_lev[L] = (long long)D.lev[L].dim[0] * D.lev[L].dim[1] * D.lev[L].dim[2];
+    if (n_lev[0] > (1ll << 27)) return fail(HK_ERR_INVALID, at + "a field of more than 2^27 blocks of 8^3 voxels");
+    const size_t nx = (size_t)F.res[0], ny = (size_t)F.res[1], b_field = nx * ny * (size_t)F.res[2] * sizeof(float);
+    D.fast = F.layout == HK_DENSE_X_FASTEST ? 0 : 2;
+    if (D.fast == 0) D.stride[0] = 1, D.stride[1] = (long long)nx, D.stride[2] = (long long)(nx * ny);
+    else D.stride[0] = (long long)(ny * (size_t)F.res[2]), D.stride[1] = F.res[2], D.stride[2] = 1;
+    hk_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    KnobScope knobs(&c->knobs);
+    // the working set: control record, then per level flags, slots, list and tile sums
+    size_t work = staged(sizeof(DDenseCtl)), o_flags[3], o_slot[3], o_list[3], o_sums[3];
+    for (int L = 0; L < 3; ++L) {
+        DDenseLevel& V = D.lev[L];
+        V.n = (uint32_t)n_lev[L];
+        V.tiles = (V.n + (uint32_t)HK_DENSE_SCAN_TILE - 1u) / (uint32_t)HK_DENSE_SCAN_TILE;
+        o_flags[L] = work, work += staged(V.n);
+        o_slot[L] = work, work += staged((size_t)V.n * 4);
+        o_list[L] = work, work += staged((size_t)V.n * 4);
+        o_sums[L] = work, work += staged((size_t)V.tiles * 4);
+    }
+    if (s->dense_work.bytes < work) HIP_TRY(s->dense_work.alloc(work));
+    if (!F.on_device && s->dense_field.bytes < b_field) HIP_TRY(s->dense_field.alloc(b_field));
+    char* wk = s->dense_work.as<char>();
+    D.ctl = reinterpret_cast<DDenseCtl*>(wk);
+    for (int L = 0; L < 3; ++L) {
+        D.lev[L].flags = reinterpret_cast<unsigned char*>(wk + o_flags[L]);
+        D.lev[L].slot = reinterpret_cast<uint32_t*>(wk + o_slot[L]);
+        D.lev[L].list = reinterpret_cast<uint32_t*>(wk + o_list[L]);
+        D.lev[L].sums = reinterpret_cast<uint32_t*>(wk + o_sums[L]);
+    }
+    // one staging block: the record, the control record coming back, then a host field on its way to the device
+    const size_t o_ctl = staged(sizeof(DMedium)), o_field = o_ctl + staged(sizeof(DDenseCtl));
+    hk_scene::Staging* st = nullptr;
+    if (int e = acquire_staging(s, o_field + (F.on_device ? 0 : staged(b_field)), st)) return e;
+    if (int e = join_lanes(c)) return e;   // noted calls render the old medium; the lanes finish before the stream rewrites it
+    char* h = static_cast<char*>(st->host);
+    D.data = F.data;
+    if (!F.on_device) {
+        std::memcpy(h + o_field, F.data, b_field);
+        HIP_TRY(hipMemcpyAsync(s->dense_field.p, h + o_field, b_field, hipMemcpyHostToDevice, c->stream));
+        D.data = s->dense_field.as<float>();
+    }
+    hk::launch_dense_count(c->stream, D);
+    HIP_TRY(hipGetLastError());
+    // the one wait: node counts, the leaves' bounds and the non-finite flag
+    DDenseCtl& ctl = *reinterpret_cast<DDenseCtl*>(h + o_ctl);
+    HIP_TRY(hipMemcpyAsync(&ctl, D.ctl, sizeof ctl, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (ctl.nonfinite) return fail(HK_ERR_INVALID, at + "non-finite voxel");
+    for (int L = 0; L < 3; ++L)
+        if ((long long)ctl.count[L] > n_lev[L] || (ctl.count[L] == 0u) != (ctl.count[0] == 0u))
+            return fail(HK_ERR_DEVICE, at + "the device builder reported inconsistent node counts (the scene is unchanged)");
+    // the tree's sections as build_nanovdb_from_dense lays them out, and the record of such a tree
+    const long long n_leaf = ctl.count[0], n_lower = ctl.count[1], n_upper = ctl.count[2];
+    D.section[2] = hknv::ROOT_HEADER + n_upper * hknv::ROOT_TILE;
+    D.section[1] = D.section[2] + n_upper * hknv::UPPER_SIZE;
+    D.section[0] = D.section[1] + n_lower * hknv::LOWER_SIZE;
+    m.nvdb_size = D.section[0] + n_leaf * hknv::LEAF_SIZE;
+    m.root_offset_1based = 1, m.upper_offset_1based = D.section[2] + 1, m.lower_offset_1based = D.section[1] + 1;
+    m.leaf_offset_1based = n_leaf ? D.section[0] + 1 : 1;
+    m.upper_count = (int)n_upper, m.lower_count = (int)n_lower, m.leaf_count = (int)n_leaf, m.root_table_size = (int)n_upper;
+    NvdbPlan plan;
+    for (int k = 0; k < 3; ++k) {
+        m.index_bbox_min[k] = D.index_min[k] = n_leaf ? (0x7fffffff - ctl.lo_enc[k]) * 8 : 0;
+        m.index_bbox_max[k] = D.index_max[k] = n_leaf ? ctl.hi1[k] * 8 : 0;   // the largest leaf origin + 8
+        // nvdb_block_extent of this tree: its leaves lie inside the index bounding box, every tile holds the background
+        const int lo = m.index_bbox_min[k] >> 3, hi = m.index_bbox_max[k] >> 3;
+        plan.nvb_min[k] = lo - 1, plan.nvb_dim[k] = hi - lo + 3;
+    }
+    plan.background = 0.0f;
+    if (plan_nanovdb_shape(m.nvdb_size, plan) != HK_OK) return fail(HK_ERR_INVALID, at + g_err);
+    DMedium o = hm.d;
+    bake_medium_fields(c->r2s_host, m, o);
+    plan.fill(o);
+    o.nv_bricks = plan.bricks ? reinterpret_cast<const float*>(&plan) : nullptr;   // (for the class check; the buffer's address follows)
+    {
+        std::string bad = media_class_refusal(s, idx, o);
+        if (!bad.empty()) return fail(HK_ERR_INVALID, at + bad);
+    }
+    const size_t need[3] = {(size_t)m.nvdb_size, (size_t)plan.total * sizeof(uint2), plan.bricks ? (size_t)plan.total * 729 * sizeof(float) : 0};
+    if (int e = fit_nanovdb_buffers(c, hm, need)) return e;
+    o.nvdb = hm.nvdb->as<unsigned char>();
+    o.nv_blocks = hm.blocks->as<uint2>();
+    o.nv_bricks = plan.bricks ? hm.bricks->as<float>() : nullptr;
+    D.tree = hm.nvdb->as<unsigned char>();
+    D.table = hm.blocks->as<uint2>();
+    for (int k = 0; k < 3; ++k) D.nvb_min[k] = plan.nvb_min[k], D.nvb_dim[k] = plan.nvb_dim[k];
+    hk::launch_dense_emit(c->stream, D, ctl.count, (size_t)m.nvdb_size);
+    DIndexBox ib;
+    for (int k = 0; k < 3; ++k) ib.lo[k] = m.index_bbox_min[k], ib.hi[k] = m.index_bbox_max[k];
+    hk::launch_majorant_nanovdb(c->stream, o, ib);
+    if (plan.bricks) hk::launch_nvdb_bricks(c->stream, o, (size_t)plan.total);
+    HIP_TRY(hipGetLastError());
+    std::memcpy(h, &o, sizeof o);
+    HIP_TRY(hipMemcpyAsync(s->media.as<DMedium>() + idx, h, sizeof o, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipEventRecord(st->ev, c->stream));
+    hm.rec = m;
+    hm.d = o;
+    return HK_OK;
+}
+
+extern "C" int32_t hk_scene_medium_tree_copy(hk_scene* s, int32_t idx, hk_medium* record_out, int64_t* n_bytes, uint8_t* bytes, int32_t* table_dims, int32_t* table_min, uint32_t* table) {
+    if (!s || !n_bytes) return fail(HK_ERR_INVALID, "hk_scene_medium_tree_copy: null argument");
+    if (idx < 0 || idx >= (int)s->h_media.size()) return fail(HK_ERR_INVALID, "hk_scene_medium_tree_copy: medium index out of range");
+    const hk_scene::Medium& hm = s->h_media[idx];
+    if (hm.rec.kind != HK_MEDIUM_NANOVDB) return fail(HK_ERR_INVALID, "hk_scene_medium_tree_copy: not a NanoVDB medium");
+    if (record_out) {
+        *record_out = hm.rec;
+        record_out->density = record_out->sigma_a_grid = record_out->sigma_s_grid = record_out->Le_grid = record_out->majorant = nullptr;
+        record_out->nvdb_bytes = nullptr;
+    }
+    *n_bytes = hm.rec.nvdb_size;
+    for (int k = 0; k < 3; ++k) {
+        if (table_dims) table_dims[k] = hm.d.nvb_dim[k];
+        if (table_min) table_min[k] = hm.d.nvb_min[k];
+    }
+    if (!bytes && !table) return HK_OK;
+    hk_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    KnobScope knobs(&c->knobs);
+    if (int e = join_lanes(c)) return e;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (bytes) HIP_TRY(hipMemcpy(bytes, hm.d.nvdb, (size_t)hm.rec.nvdb_size, hipMemcpyDeviceToHost));
+    if (table) HIP_TRY(hipMemcpy(table, hm.d.nv_blocks, (size_t)hm.d.nvb_dim[0] * hm.d.nvb_dim[1] * hm.d.nvb_dim[2] * sizeof(uint2), hipMemcpyDeviceToHost));
     return HK_OK;
 }
 

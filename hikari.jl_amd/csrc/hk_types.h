@@ -159,6 +159,42 @@ struct DIndexBox {
     int lo[3], hi[3];
 };
 
+// ---- hk_scene_update_medium_dense: a NanoVDB tree built on the device from a dense field (hk_nvdb_build.h) ----
+// The one record the host reads back: node counts per level (0 leaves, 1 lower, 2 upper nodes), the bounds of the leaves in BLOCK
+// coordinates (lo_enc = 0x7fffffff - the smallest, hi1 = the largest + 1: both are integer maxima over a zeroed word) and the flag
+// of a non-finite voxel.
+struct DDenseCtl {
+    uint32_t count[3];
+    int lo_enc[3], hi1[3];
+    int nonfinite;
+};
+// a level of the tree as flags: one byte per possible node of the field's extent, [x][y][z] z fastest — the order the nodes are
+// numbered in; slot[i] = the number of set flags before i; list[slot[i]] = i for a set flag; sums: per HK_DENSE_SCAN_TILE flags
+enum { HK_DENSE_SCAN_TILE = 4096 };
+struct DDenseLevel {
+    unsigned char* flags;
+    uint32_t* slot;
+    uint32_t* list;
+    uint32_t* sums;
+    int dim[3];
+    uint32_t n, tiles;   // dim[0] * dim[1] * dim[2] and ceil(n / HK_DENSE_SCAN_TILE)
+};
+struct DDense {
+    const float* data;
+    int res[3];
+    long long stride[3];   // of x, y, z in floats
+    int fast;              // the axis of stride 1: 0 (HK_DENSE_X_FASTEST) or 2 (HK_DENSE_Z_FASTEST)
+    DDenseLevel lev[3];
+    DDenseCtl* ctl;
+    // set after the one wait, for the kernels that write the tree: 0-based byte positions of the three node sections, the tree, the
+    // index bounding box of the root header, and the block table with its extent
+    unsigned char* tree;
+    long long section[3];  // leaf, lower, upper nodes
+    int index_min[3], index_max[3];
+    uint2* table;
+    int nvb_min[3], nvb_dim[3];
+};
+
 struct DMediumInterface {
     int material, inside, outside, pad;
 };

@@ -319,6 +319,16 @@ def _lower_off(c):
     return (((x >> 3) & 15) << 8) | (((y >> 3) & 15) << 4) | ((z >> 3) & 15)
 
 
+def _ordered_min_max(vals):
+    """Minimum and maximum of finite float32 values as Julia's `min` / `max` give them (nanovdb.jl:714-722): -0.0 orders below +0.0.
+    numpy's `min()` / `max()` leave the sign of a zero result to the order of their reduction, so the comparison is made on the
+    order-preserving integer key of the bits — the rule the device builder (hk_nvdb_build.h) follows too."""
+    flip = lambda k: k ^ ((k >> 31) & np.int32(0x7fffffff))      # a negative value: the magnitude bits reversed in order; its own inverse
+    keys = flip(np.ascontiguousarray(vals, dtype=f32).view(np.int32))
+    ends = flip(np.array([keys.min(), keys.max()], dtype=np.int32)).view(f32)
+    return ends[0], ends[1]
+
+
 def build_nanovdb_from_dense(data, origin, extent, background=0.0):
     """nanovdb.jl:602-858.  data[nx, ny, nz] float32 -> (buffer uint8[], metadata dict).  Buffer layout
     [Root | Upper nodes | Lower nodes | Leaf nodes], child offsets relative to the parent, 0-based positions
@@ -375,8 +385,9 @@ def build_nanovdb_from_dense(data, origin, extent, background=0.0):
         active = vals != background
         bits = np.packbits(active.astype(np.uint8), bitorder="little")
         buf[off + LEAF_MASK_OFF:off + LEAF_MASK_OFF + 64] = bits
-        w32(off + LEAF_MIN_OFF, vals.min(), f32)
-        w32(off + LEAF_MIN_OFF + 4, vals.max(), f32)
+        vmin, vmax = _ordered_min_max(vals)
+        w32(off + LEAF_MIN_OFF, vmin, f32)
+        w32(off + LEAF_MIN_OFF + 4, vmax, f32)
         buf[off + LEAF_VALUES:off + LEAF_VALUES + 2048] = vals.view(np.uint8)
     for low_i, lb in enumerate(lower_bases):
         off = lower_pos(low_i)
@@ -607,11 +618,83 @@ class NanoVDBMedium(_HostMajorant, Medium):
     def max_density(self):
         return float(self.majorant.max())
 
-    def update(self, data=None, filepath=None, bounds=None, sigma_a=None, sigma_s=None, g=None, transform=None, majorant_res=None):
+    # The host tree.  update(build="device") only keeps the field: the device builds the tree of a device scene
+    # (hk_scene_update_medium_dense), and the host tree, its metadata and the host majorant are built when something asks for them — a
+    # device scene created from the kept description, save(), buffer, meta, max_density — as _HostMajorant builds the majorant.
+    _field = None
+
+    def _host_tree(self):
+        if self._field is not None:
+            field, self._field = self._field, None
+            if not isinstance(field, np.ndarray):
+                field = field.detach().cpu().numpy()
+            extent = tuple(float(f32(self.bounds[1][k]) - f32(self.bounds[0][k])) for k in range(3))
+            self._buffer, self._meta = build_nanovdb_from_dense(field, self.bounds[0], extent)
+
+    @property
+    def buffer(self):
+        self._host_tree()
+        return self._buffer
+
+    @buffer.setter
+    def buffer(self, value):
+        self._buffer = value
+
+    @property
+    def meta(self):
+        self._host_tree()
+        return self._meta
+
+    @meta.setter
+    def meta(self, value):
+        self._meta = value
+
+    def dense_field(self, keep):
+        """The field of a pending update(build="device") as hk_scene_update_medium_dense takes it (None: there is none): a numpy array
+        as it is (HK_DENSE_Z_FASTEST, host memory), a torch tensor through its data_ptr() (memory of its device)."""
+        field = self._field
+        if field is None:
+            return None
+        rec = A.hk_dense_field()
+        rec.res[:] = tuple(int(v) for v in field.shape)
+        rec.layout = A.HK_DENSE_Z_FASTEST
+        keep.append(field)
+        if isinstance(field, np.ndarray):
+            rec.data, rec.on_device = field.ctypes.data_as(A.PF), 0
+        else:
+            rec.data, rec.on_device = C.cast(C.c_void_p(field.data_ptr()), A.PF), 1
+        return rec
+
+    def _update_device_field(self, data):
+        """the checks of update(build="device") on the field; -> what is kept"""
+        if isinstance(data, np.ndarray) or not hasattr(data, "data_ptr"):
+            data = np.ascontiguousarray(data, dtype=f32)
+            if data.ndim != 3 or 0 in data.shape:
+                raise ValueError("update: data must be [nx, ny, nz]")
+            if not np.isfinite(data).all():
+                raise ValueError("update: non-finite voxel")
+            return data
+        import torch
+        if data.ndim != 3 or 0 in data.shape:
+            raise ValueError("update: data must be [nx, ny, nz]")
+        if not data.is_cuda:
+            raise ValueError("update: a torch tensor must live on the device (hand a host field over as a numpy array)")
+        return data.detach().to(torch.float32).contiguous()    # (the device looks for non-finite voxels)
+
+    def update(self, data=None, filepath=None, bounds=None, sigma_a=None, sigma_s=None, g=None, transform=None, majorant_res=None, build="host"):
         """A new tree in place — from a dense field (`data`, placed in `bounds` or the bounds the medium has) or from a file (`filepath`,
         with `transform` as in from_file) — and / or new coefficients.  The tree may be of any size.  Raises ValueError for a changed
-        majorant resolution, both sources at once and non-finite values."""
+        majorant resolution, both sources at once and non-finite values.
+        build="device" (with `data`: a numpy array [nx, ny, nz] or a torch tensor on the device): the tree is not built here; the field
+        is kept, a device scene builds its tree from it (Scene.update_medium), and the host tree is built when it is first asked for.
+        The field is kept BY REFERENCE when it already is a contiguous float32 array or tensor (no copy is made of 33 MB per time
+        step): what is written into it afterwards is what a late host tree is built from, so hand over a copy of a buffer that a
+        simulation goes on writing into — or ask for `buffer` first."""
         _same_res("majorant_res", majorant_res, self.majorant_res)
+        if build not in ("host", "device"):
+            raise ValueError("update: build must be \"host\" or \"device\"")
+        if build == "device" and (filepath is not None or data is None):
+            raise ValueError("update: build=\"device\" builds the tree of a dense field (data=...), not of a file")
         if data is not None and filepath is not None:
             raise ValueError("update: give data or filepath, not both")
         if filepath is None and transform is not None:
@@ -621,10 +704,17 @@ class NanoVDBMedium(_HostMajorant, Medium):
         if g is not None and not np.isfinite(g):
             raise ValueError("update: non-finite g")
         b = _checked_bounds(bounds) if bounds is not None else None
-        if data is not None and not np.isfinite(np.asarray(data, dtype=f32)).all():
+        if build == "device":
+            data = self._update_device_field(data)
+        elif data is not None and not np.isfinite(np.asarray(data, dtype=f32)).all():
             raise ValueError("update: non-finite voxel")
-        if filepath is not None:
+        if build == "device":
+            if b is not None:
+                self.bounds = b
+            self._field, self._buffer, self._meta, self.majorant = data, None, None, None
+        elif filepath is not None:
             new = type(self).from_file(filepath, self.sigma_a, self.sigma_s, self.g, transform, self.majorant_res)
+            self._field = None
             self.buffer, self.meta, self.bounds = new.buffer, new.meta, new.bounds
             self.majorant = new._majorant
         elif data is not None or b is not None:
@@ -635,6 +725,7 @@ class NanoVDBMedium(_HostMajorant, Medium):
                 data = self.meta["dense"][:nx, :ny, :nz]
             bb = b if b is not None else self.bounds
             extent = tuple(float(f32(bb[1][k]) - f32(bb[0][k])) for k in range(3))
+            self._field = None
             self.buffer, self.meta = build_nanovdb_from_dense(data, bb[0], extent)
             self.bounds, self.majorant = bb, None
         for name, v in (("sigma_a", sigma_a), ("sigma_s", sigma_s), ("g", g)):
@@ -668,12 +759,15 @@ class NanoVDBMedium(_HostMajorant, Medium):
             raise ValueError("this medium already holds a full file buffer; write self.buffer with zlib instead")
         save_nanovdb(filepath, self.buffer, self.meta)
 
-    def fill_record(self, rec, keep, majorant=True):
+    def fill_record(self, rec, keep, majorant=True, tree=True):
+        """tree=False: only what hk_scene_update_medium_dense reads (nothing of the host tree is touched, or built)"""
         _base_record(rec, self.kind, self.sigma_a, self.sigma_s, RGBSpectrum(0.0), self.g)
-        m = self.meta
         rec.bounds_min[:] = self.bounds[0]
         rec.bounds_max[:] = self.bounds[1]
         rec.majorant_res[:] = self.majorant_res
+        if not tree:
+            return
+        m = self.meta
         rec.majorant = self.majorant.ctypes.data_as(A.PF) if majorant else None
         keep.append(self._majorant)
         rec.max_density = self.max_density if majorant else 0.0

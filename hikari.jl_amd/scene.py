@@ -396,7 +396,12 @@ class Scene:
     def update_medium(self, medium, **changes):
         """New volume data, coefficients, bounds or transform for a medium of this scene (the keywords of the medium's own update()),
         in the kept description and in every device scene — which builds the majorant grid, its zero-cell mask and the NanoVDB bricks
-        from the data itself (hk_scene_update_medium); the host majorant of `medium` is rebuilt only when a scene is created again."""
+        from the data itself (hk_scene_update_medium); the host majorant of `medium` is rebuilt only when a scene is created again.
+        A NanoVDBMedium's data=..., build="device" (a numpy array, or a torch tensor on the device of the scene's context) lets the
+        device scenes build the tree as well (hk_scene_update_medium_dense); the medium keeps the field and builds its host tree late.
+        A tensor is read in place by the scenes of a context (Context.get) on the tensor's device — which is waited for, so the device
+        has read the tensor when this returns — and goes from host memory to every other scene.  The medium keeps the field BY
+        REFERENCE for its late host tree (media.NanoVDBMedium.update): hand over a copy if the array is written again."""
         for idx, m in enumerate(self.media):
             if m is medium:
                 break
@@ -416,9 +421,36 @@ class Scene:
         self._stale_media.add(idx)             # the kept record is refilled, with the host majorant, when a scene is created from it
         keep = []
         rec = A.hk_medium()
-        medium.fill_record(rec, keep, majorant=False)
         from . import _lib
-        for h in (getattr(self, "_device", None) or {}).values():
+        handles = list((getattr(self, "_device", None) or {}).values())
+        field = medium.dense_field(keep) if changes.get("build") == "device" else None
+        if field is not None:
+            # the device builds the tree from the field (hk_scene_update_medium_dense); the host tree waits until something asks for it
+            medium.fill_record(rec, keep, majorant=False, tree=False)
+            from_host = field
+            if field.on_device:
+                # A tensor is read in place only by a scene whose context is on the tensor's device; every other scene gets the field
+                # from host memory.  The tensor's producer is ordered before the library's stream here, and the context is waited for
+                # after the call, so the build kernels have read the tensor when this returns: the caller may write into it again.
+                import torch
+                from .volpath import Context
+                tensor = keep[0]
+                torch.cuda.current_stream(tensor.device).synchronize()
+                ctx_of = {id(c): c for c in Context._by_device.values()}
+                local = {cid for cid in self._device if cid in ctx_of and int(ctx_of[cid].device) == int(tensor.device.index or 0)}
+                if len(local) < len(self._device):
+                    host = np.ascontiguousarray(tensor.cpu().numpy())
+                    keep.append(host)
+                    from_host = A.hk_dense_field.from_buffer_copy(field)
+                    from_host.data, from_host.on_device = host.ctypes.data_as(A.PF), 0
+            for cid, h in (getattr(self, "_device", None) or {}).items():
+                in_place = field.on_device and cid in local
+                _lib.check(_lib.lib().hk_scene_update_medium_dense(h, idx, C.byref(rec), C.byref(field if in_place else from_host)), "hk_scene_update_medium_dense")
+                if in_place:
+                    _lib.check(_lib.lib().hk_sync(ctx_of[cid].h), "hk_sync")
+            return
+        medium.fill_record(rec, keep, majorant=False)
+        for h in handles:
             _lib.check(_lib.lib().hk_scene_update_medium(h, idx, C.byref(rec)), "hk_scene_update_medium")
 
     def _refresh_media(self):

@@ -441,6 +441,43 @@ int32_t hk_scene_update_lights(hk_scene* scene, int32_t first, int32_t n, const 
 int32_t hk_scene_update_envmap(hk_scene* scene, int32_t idx, const float* data, const float* rotation);
 int32_t hk_scene_update_medium(hk_scene* scene, int32_t idx, const hk_medium* medium);
 
+/* hk_scene_update_medium_dense: NanoVDB medium `idx` becomes the tree of a dense density field, and the tree is built ON THE DEVICE.
+ * Of *medium the call reads kind, sigma_a, sigma_s, Le, g, bounds_min, bounds_max and majorant_res (which must be unchanged) — and, like
+ * hk_scene_update_medium, the two transforms; every NanoVDB field (nvdb_bytes, nvdb_size, offsets, counts, inv_mat, vec, index_bbox_*),
+ * majorant and max_density are ignored.  The map is derived on the host in binary32, as the reference's dense builder derives it
+ * (nanovdb.jl:602-858):
+ *   d[k] = (bounds_max[k] - bounds_min[k]) / (float)res[k];   inv_mat = diag(1.0f / d[k]);   vec[k] = bounds_min[k] + d[k] / 2.0f
+ * THE CONTRACT: after the call the scene holds, bit for bit, what it holds after hk_scene_update_medium with the tree that builder makes
+ * of the same field (background 0): the tree bytes [root header and tiles | upper | lower | leaf nodes], every byte that is not written
+ * being 0; offsets, counts and index bounding box of the record; the block table, its extent and background; majorant grid, zero-cell
+ * mask and halo bricks.  The rules the bytes follow:
+ *   leaf          an 8^3 block (blocks that stick out of res are padded with 0) with any voxel != 0.0f; -0.0f is background.  Its value
+ *                 mask has bit (lx << 6) | (ly << 3) | lz for every voxel != 0.0f; min and max are those of the 512 values, -0.0f
+ *                 ordered below +0.0f
+ *   order         leaves, lower nodes (16^3 blocks) and upper nodes (32^3 lower nodes) are numbered in lexicographic (x, y, z) order of
+ *                 their origins, z fastest; a child offset is relative to its parent, a root tile's to the root (key, child, state 1,
+ *                 value 0)
+ *   bounding box  the integer minimum of the leaf origins, and their maximum + 8; all 0 without a leaf (a tree of 64 bytes)
+ * The field is read in place when it is on the device; a host field crosses once, through the scene's pinned memory, and nothing else
+ * does: the block table is built on the device too.  The call accepts and refuses what hk_scene_update_medium would for that tree, with
+ * the same status (the media classes against HK_NVDB_DENSE_MB, more than 2^27 blocks in the table, 4 GiB of tree), and also: a null
+ * argument or field, a medium that is not NanoVDB, a res below 1 or a field of more than 2^27 blocks, an unknown layout, a non-finite
+ * voxel (found on the device, for both kinds of source).  A refused call leaves the scene as it was.
+ * The call WAITS FOR THE DEVICE ONCE, for one record: the node counts, the leaves' bounds and the non-finite flag, which size the tree and
+ * the table and decide the class check.  Buffers are reused while the new tree fits and grow as in hk_scene_update_medium.  Like every
+ * edit it renders the noted calls first and does not clear films. */
+enum { HK_DENSE_X_FASTEST = 0,   /* Julia [nx,ny,nz], the layout of hk_medium::density */
+       HK_DENSE_Z_FASTEST = 1 }; /* C [nx][ny][nz], a numpy / torch array as it is      */
+typedef struct hk_dense_field {
+    const float* data;
+    int32_t res[3];      /* nx, ny, nz >= 1; may differ from the last update's */
+    int32_t layout;
+    int32_t on_device;   /* 0: host memory, borrowed for the call, staged through the scene's pinned memory.
+                            1: memory of ctx's device, already visible to ctx's stream (the caller has ordered its
+                               producer before the call); read by the build kernels, not kept after they ran */
+} hk_dense_field;
+int32_t hk_scene_update_medium_dense(hk_scene* scene, int32_t idx, const hk_medium* medium, const hk_dense_field* field);
+
 int32_t hk_integrator_create(hk_ctx* ctx, const hk_integrator_params* params, hk_integrator** out);
 int32_t hk_integrator_destroy(hk_integrator* integ);
 
@@ -464,7 +501,7 @@ int32_t hk_film_clear(hk_film* film); /* clear!(vp), volpath.jl:108-113 */
  *     following on) are rendered as ONE pass — bit-identical film, a seventh of the time — when the note reaches HK_BATCH_PATHS_M
  *     (64 M paths), when a call comes that does not continue it, or when anything looks: hk_flush, hk_sync, every hk_film_* / hk_stats_* /
  *     hk_*_destroy / hk_ctx_set_option /
- *     hk_scene_set_transform / hk_scene_set_vertices / hk_scene_update_materials / hk_scene_update_lights / hk_scene_update_envmap / hk_scene_update_medium entry point.  hk_flush enqueues the noted calls without waiting for them.
+ *     hk_scene_set_transform / hk_scene_set_vertices / hk_scene_update_materials / hk_scene_update_lights / hk_scene_update_envmap / hk_scene_update_medium / hk_scene_update_medium_dense entry point.  hk_flush enqueues the noted calls without waiting for them.
  *     HK_BATCH_PATHS_M=0 (hk_ctx_set_option) turns the noting off.
  * Argument errors are reported by the call itself; a device error of a deferred pass by the call that flushes it — also by the
  * destroy entry points, which still destroy their object. */
@@ -692,6 +729,12 @@ int32_t hk_scene_rebuild_bvh(hk_scene* scene);
 /* The majorant grid (n_cells floats, index x + rx*(y + ry*z)) and the zero-cell mask ((n_cells + 31) / 32 words, bit c of the mask = cell c)
    of medium `idx` as the device holds them; waits for the context's stream.  Either array may be NULL; n_cells = 0 for a homogeneous medium. */
 int32_t hk_scene_medium_copy(hk_scene* scene, int32_t idx, int32_t* n_cells, float* majorant, uint32_t* zero_mask);
+/* The tree of NanoVDB medium `idx` as the device holds it, whichever call put it there: *record_out (NULL: not wanted) = the record with
+   its offsets, counts, inv_mat, vec and index bounding box, every pointer NULL; *n_bytes = the size of the tree; table_dims / table_min
+   (3 each, or NULL) = extent and origin of the block table in blocks.  Call once for the sizes, then with `bytes` (*n_bytes of them)
+   and / or `table` (2 words per block: leaf offset and value bits, block (bx, by, bz) at bz + dims[2]*(by + dims[1]*bx)); either may be
+   NULL.  A call that copies waits for the context's stream. */
+int32_t hk_scene_medium_tree_copy(hk_scene* scene, int32_t idx, hk_medium* record_out, int64_t* n_bytes, uint8_t* bytes, int32_t* table_dims, int32_t* table_min, uint32_t* table);
 /* The halo bricks of NanoVDB medium `idx` as the device holds them: dims[3] = the block table's extent (all 0 when the medium has no
    bricks), out (NULL: only the extent) = dims[0]*dims[1]*dims[2] bricks of 729 floats, block (bx, by, bz) at bz + dims[2]*(by + dims[1]*bx). */
 int32_t hk_test_medium_bricks(hk_scene* scene, int32_t idx, int32_t* dims, float* out);

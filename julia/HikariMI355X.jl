@@ -714,6 +714,61 @@ function update_medium!(vp::MI355XVolPath, index::Integer, medium)
     nothing
 end
 
+# hk_dense_field of the header (no Hk prefix: the mirrors named Hk* are those of the scene description)
+struct DenseFieldRecord
+    data::Ptr{Float32}
+    res::NTuple{3,Int32}
+    layout::Int32
+    on_device::Int32
+end
+const HK_DENSE_X_FASTEST, HK_DENSE_Z_FASTEST = Int32(0), Int32(1)
+
+"""
+    update_medium_dense!(vp, index, data; bounds, sigma_a, sigma_s, g = 0f0)
+
+NanoVDB medium `index` (0-based) of the scene on the devices becomes the tree of the dense field `data` (`Array{Float32,3}`, `[nx, ny, nz]`,
+handed over as it is: `HK_DENSE_X_FASTEST`), placed in `bounds`.  The library builds the tree, its block table, the majorant grid and
+the bricks on the device — what `update_medium!` with `NanoVDBMedium(data; bounds, ...)` leaves there, without the host tree build.
+The majorant resolution cannot change in place: it is read from the record the device scene keeps.
+"""
+function update_medium_dense!(vp::MI355XVolPath, index::Integer, data::AbstractArray{<:Real,3}; bounds, sigma_a, sigma_s, g = 0f0)
+    field = Array{Float32,3}(data)
+    nul, nul8 = Ptr{Float32}(C_NULL), Ptr{UInt8}(C_NULL)
+    record(mres) = HkMedium(HK_MEDIUM_NANOVDB, rgba(sigma_a), rgba(sigma_s), (0f0, 0f0, 0f0, 1f0), Float32(g), 1f0, 1f0, tup3(bounds.p_min), tup3(bounds.p_max), Z16, Z16, I3Z, nul, nul, nul, nul,
+                            mres, nul, 0f0, nul8, 0, 0, 0, 0, 0, 0, 0, 0, 0, Z9, Z3, I3Z, I3Z)
+    GC.@preserve field begin
+        dense = DenseFieldRecord(pointer(field), i3(size(field)), HK_DENSE_X_FASTEST, Int32(0))
+        for d in vp.devs
+            d.scene == C_NULL && continue
+            kept, n = Ref(record(I3Z)), Ref{Int64}(0)               # the medium as the device scene holds it: its majorant_res
+            check(ccall((:hk_scene_medium_tree_copy, LIB), Int32, (Ptr{Cvoid}, Int32, Ref{HkMedium}, Ref{Int64}, Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}, Ptr{UInt32}), d.scene, Int32(index), kept, n,
+                        Ptr{UInt8}(C_NULL), Ptr{Int32}(C_NULL), Ptr{Int32}(C_NULL), Ptr{UInt32}(C_NULL)), "hk_scene_medium_tree_copy")
+            check(ccall((:hk_scene_update_medium_dense, LIB), Int32, (Ptr{Cvoid}, Int32, Ref{HkMedium}, Ref{DenseFieldRecord}), d.scene, Int32(index), record(kept[].majorant_res), dense),
+                  "hk_scene_update_medium_dense")
+        end
+    end
+    nothing
+end
+
+"""
+    medium_tree(vp, index) -> (bytes, table, table_dims, table_min)
+
+The NanoVDB tree of medium `index` as the first device holds it (whichever update put it there) and its block table
+(`2 x dims[3] x dims[2] x dims[1]` words: leaf offset and value bits per block, z fastest).
+"""
+function medium_tree(vp::MI355XVolPath, index::Integer)
+    d = first(vp.devs)
+    n = Ref{Int64}(0)
+    dims, tmin = zeros(Int32, 3), zeros(Int32, 3)
+    check(ccall((:hk_scene_medium_tree_copy, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ref{Int64}, Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}, Ptr{UInt32}), d.scene, Int32(index), C_NULL, n,
+                Ptr{UInt8}(C_NULL), dims, tmin, Ptr{UInt32}(C_NULL)), "hk_scene_medium_tree_copy")
+    bytes = zeros(UInt8, n[])
+    table = zeros(UInt32, 2, dims[3], dims[2], dims[1])
+    check(ccall((:hk_scene_medium_tree_copy, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ref{Int64}, Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}, Ptr{UInt32}), d.scene, Int32(index), C_NULL, n,
+                bytes, dims, tmin, table), "hk_scene_medium_tree_copy")
+    bytes, table, dims, tmin
+end
+
 """
     set_vertices!(vp, first_tri, positions; normals = nothing, uvs = nothing)
 
