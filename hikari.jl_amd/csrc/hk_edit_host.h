@@ -1,6 +1,6 @@
 // hk_edit_host.h — the host arithmetic of hk_scene_set_vertices and hk_scene_bvh_cost that needs no device: staging a range of new
 // positions (finite check, copy, bounds per block of triangles in one pass), folding those bounds into hk_scene::block_box, and the
-// cost of a tree from its float child boxes.  Plain C++ (tests/native/vertex_edit_check.cpp builds it alone, under the sanitizers);
+// cost of a tree from its float child boxes; and whether the material records hold a MixMaterial.  Plain C++ (tests/native/vertex_edit_check.cpp builds it alone, under the sanitizers);
 // hk_node_cost is also what the device reduction (k_bvh_cost) evaluates per node, so both sides round alike.
 #pragma once
 #include <algorithm>
@@ -38,6 +38,23 @@ HK_EDIT_HD inline double hk_root_area(const float lo[2][3], const float hi[2][3]
 }
 
 namespace hk {
+
+// DScene::has_mix from the material records as created / last updated (hk_material: `kind`); hk_scene_create and
+// hk_scene_update_materials both ask this, over ALL records, so the flag cannot drift from them.
+template <class Material>
+inline int materials_have_kind(const Material* m, size_t n, int kind) {
+    for (size_t i = 0; i < n; ++i)
+        if (m[i].kind == kind) return 1;
+    return 0;
+}
+// DScene::single_kind: the one material kind of a scene without a MixMaterial whose non-Mix records (kinds_mask: bit k = a record of
+// kind k) are all of that kind and which has a queue (kind < max_kinds); -1 otherwise.
+inline int single_material_kind(unsigned kinds_mask, int has_mix, int max_kinds) {
+    if (has_mix || kinds_mask == 0u || (kinds_mask & (kinds_mask - 1u)) != 0u) return -1;
+    int k = 0;
+    while (!((kinds_mask >> k) & 1u)) ++k;
+    return k < max_kinds ? k : -1;
+}
 
 // Copies the 9 * n floats of triangles [first, first + n) to `dst` and, when `block` > 0, notes lo[3] hi[3] of every block of `block`
 // triangles the range touches in `fresh` (block first / block comes first).  false: a position is not finite (dst and fresh are then

@@ -943,7 +943,12 @@ enum { LR_EMPTY = 0, LR_ACTIVE = 1 };
 
 // STACK: LDS stack entries per lane.  The stack holds at most one entry per inner level, so a BVH of depth <= 16 (every scene
 // but the 10^6-triangle one) runs with half the LDS: 16 KB per block instead of 32, and LDS stops limiting residency.
-template <bool COUNT, int NC, bool QN = false, int MIN_IDLE = HK_TRACE_MIN_IDLE>
+// MIX = false: the scene has no MixMaterial (DScene::has_mix), and the flush carries neither the resolve (texture lookup, hashes, uv
+// interpolation) nor its tests — registers and scheduling of a branch never taken.
+// SINGLE (with MIX = false): every material of the scene is of ONE kind (DScene::single_kind, uniform): the flush does not load the
+// material record for its kind and pushes to that kind's queue in one step, with one count; hit, mat_id and the queue entries
+// (order, emissive flag) are written as by the general flush.
+template <bool COUNT, int NC, bool QN = false, int MIN_IDLE = HK_TRACE_MIN_IDLE, bool MIX = true, bool SINGLE = false>
 __device__ __forceinline__ void trace_lean_body(const DPathState& st, const DScene& sc, int depth, DStats* stats, const SegTickets& src, int* __restrict__ stack, const NodeCache& cache) {
     const int lane = lane_id();
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
@@ -955,9 +960,11 @@ __device__ __forceinline__ void trace_lean_body(const DPathState& st, const DSce
     const uint32_t seg = (uint32_t)gw * (uint32_t)st.wave_cap;   // the rays of this segment: entries seg .. seg + n - 1, read in order (no index queue)
     const int n = *count_ptr(st, depth, Q_RAY, gw);
     WaveQ q_escaped = wq_open(st.escaped_q, st, gw);
+    static_assert(!(SINGLE && MIX), "a scene with a MixMaterial is not a single-kind scene");
     int kind_count[HK_MAX_KINDS];
 #pragma unroll
     for (int k = 0; k < HK_MAX_KINDS; ++k) kind_count[k] = 0;
+    int one_count = 0;   // SINGLE: the entries of the one kind's queue
     int cursor = 0;
     int state = LR_EMPTY;
     uint32_t slot = 0;
@@ -978,12 +985,12 @@ __device__ __forceinline__ void trace_lean_body(const DPathState& st, const DSce
                     const DTriMeta hm = sc.meta[r.best.prim];
                     eflag = hm.arealight > 0 ? HK_MATQ_EMISSIVE : 0u;
                     int mat = sc.mis[hm.mi].material;
-                    if (sc.materials[mat].kind == HK_MAT_MIX) {   // MixMaterial is resolved here so the queue is sorted by the final kind
+                    if (MIX && sc.materials[mat].kind == HK_MAT_MIX) {   // MixMaterial is resolved here so the queue is sorted by the final kind
                         float w = 1.0f - r.best.u - r.best.v;
                         mat = resolve_mix_material(sc, mat, r.o + r.d * r.best.t, -r.d, uv_at(sc, r.best.prim, w, r.best.u, r.best.v));
                     }
-                    kind = sc.materials[mat].kind;
-                    if (kind == HK_MAT_MIX) kind = HK_MAT_FALLBACK;
+                    kind = SINGLE ? sc.single_kind : sc.materials[mat].kind;
+                    if (MIX && kind == HK_MAT_MIX) kind = HK_MAT_FALLBACK;
                     stream_st(&st.hit[slot], make_float4(r.best.t, __int_as_float(r.best.prim), r.best.u, r.best.v));
                     stream_st(reinterpret_cast<uint32_t*>(st.mat_id) + slot, (uint32_t)(mat | (hm.arealight > 0 ? HK_MAT_EMISSIVE_BIT : 0)));
                 }
@@ -991,6 +998,11 @@ __device__ __forceinline__ void trace_lean_body(const DPathState& st, const DSce
             }
             wq_push(q_escaped, slot, kind == -2);
             unsigned long long pending = __ballot(kind >= 0);
+            if (SINGLE) {   // what the loop below does in its one turn when every hit is of the same kind
+                if (kind >= 0) stream_st(&st.mat_q[((size_t)sc.single_kind * st.n_waves + gw) * st.wave_cap + one_count + __popcll(pending & lt_mask)], slot | eflag);
+                one_count += __popcll(pending);
+                pending = 0ull;
+            }
             while (pending) {
                 int src = __ffsll((long long)pending) - 1;
                 const int k = __builtin_amdgcn_readlane(kind, src);   // src is wave-uniform: the kind and every count below stay in scalar registers
@@ -1031,7 +1043,7 @@ __device__ __forceinline__ void trace_lean_body(const DPathState& st, const DSce
     if (lane == 0) {
         *count_ptr(st, depth, Q_MEDIUM, gw) = 0;
 #pragma unroll
-        for (int k = 0; k < HK_MAX_KINDS; ++k) *count_ptr(st, depth, Q_MAT0 + k, gw) = kind_count[k];
+        for (int k = 0; k < HK_MAX_KINDS; ++k) *count_ptr(st, depth, Q_MAT0 + k, gw) = SINGLE ? (k == sc.single_kind ? one_count : 0) : kind_count[k];
     }
     }
     stats += global_wave();
@@ -1043,14 +1055,14 @@ __device__ __forceinline__ void trace_lean_body(const DPathState& st, const DSce
     }
     HK_DBG_FLUSH(stats);
 }
-template <bool COUNT, int STACK, int BLOCK = HK_TRACE_BLOCK, int NC = 0, bool QN = false>
+template <bool COUNT, int STACK, int BLOCK = HK_TRACE_BLOCK, int NC = 0, bool QN = false, bool MIX = true, bool SINGLE = false>
 __global__ void __launch_bounds__(BLOCK) k_trace_lean(DPathState st, DScene sc, int depth, DStats* stats) {
     __shared__ int lds_stack[(BLOCK / 64) * STACK * 64];
     __shared__ float4 lds_box[NC > 0 ? 3 * NC : 1];
     __shared__ int2 lds_child[NC > 0 ? NC : 1];
     int* stack = lds_stack + (threadIdx.x >> 6) * (STACK * 64);
     const NodeCache cache = node_cache_fill<NC, BLOCK, QN>(sc, lds_box, lds_child);
-    trace_lean_body<COUNT, NC, QN, (NC >= 1024 ? HK_CLOSEST_MIN_IDLE_LDS : HK_TRACE_MIN_IDLE)>(st, sc, depth, stats, seg_open(st, ticket_ptr(st, depth, TK_TRACE), st.dynamic_segments != 0, depth, Q_RAY), stack, cache);
+    trace_lean_body<COUNT, NC, QN, (NC >= 1024 ? HK_CLOSEST_MIN_IDLE_LDS : HK_TRACE_MIN_IDLE), MIX, SINGLE>(st, sc, depth, stats, seg_open(st, ticket_ptr(st, depth, TK_TRACE), st.dynamic_segments != 0, depth, Q_RAY), stack, cache);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -136,6 +136,9 @@ void launch_camera(hipStream_t s, int n_cu, const DPathState& st, const DFrame& 
 #ifndef HK_SHADOW_NC32
 #define HK_SHADOW_NC32 0
 #endif
+#ifndef HK_TRACE_SINGLE_KIND   // 0: scenes of one material kind run k_trace_lean's Mix-free flush instead of the single-kind one (A/B builds)
+#define HK_TRACE_SINGLE_KIND 1
+#endif
 #ifndef HK_TRACE_NC32
 #define HK_TRACE_NC32 128   // 10^6-triangle scene: trace -1.3 % (256 nodes cost a block per CU: +15 %)
 #endif
@@ -155,9 +158,17 @@ static void lean_dispatch(const DScene& sc, const DFrame& fr, F&& launch) {
 }
 void launch_trace(hipStream_t s, int n_cu, const DPathState& st, const DScene& sc, const DTables& T, const DFrame& fr, int depth, DStats* stats) {
     if (lean_scene(sc)) {
+        // The flush of the instantiation follows the scene's materials (DScene::has_mix / single_kind, kept current by
+        // hk_scene_update_materials): 0 with the MixMaterial resolve, 1 without it, 2 without it and for ONE material kind.  The counting
+        // instantiations (count_nodes, a diagnostic) are not multiplied: they keep the general flush.
+        const int flush = sc.has_mix ? 0 : (HK_TRACE_SINGLE_KIND && sc.single_kind >= 0 ? 2 : 1);
         lean_dispatch<1024, 1536, HK_TRACE_NC32>(sc, fr, [&](auto COUNT, auto STACK, auto BLOCK, auto NC, auto QN) {
             constexpr int block = decltype(BLOCK)::value;
-            launch_resident<k_trace_lean<decltype(COUNT)::value, decltype(STACK)::value, block, decltype(NC)::value, decltype(QN)::value>>(s, n_cu, st, block, 8, sc, depth, stats);
+            constexpr bool count = decltype(COUNT)::value;
+            with_int<2, 1, 0>(flush, [&](auto FLUSH) {
+                constexpr int f = count ? 0 : decltype(FLUSH)::value;
+                launch_resident<k_trace_lean<count, decltype(STACK)::value, block, decltype(NC)::value, decltype(QN)::value, f == 0, f == 2>>(s, n_cu, st, block, 8, sc, depth, stats);
+            });
         });
         return;
     }

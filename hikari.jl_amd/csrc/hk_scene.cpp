@@ -335,6 +335,8 @@ int upload_materials(hk_scene* s, const hk_scene_desc* d, const hk::RGB2Spec& r2
         bake_material(r2s, d->materials[i], dm[i]);
         if (dm[i].kind != HK_MAT_MIX) s->kinds_mask |= 1u << dm[i].kind;
     }
+    s->d.has_mix = hk::materials_have_kind(d->materials, (size_t)d->n_materials, HK_MAT_MIX);
+    s->d.single_kind = hk::single_material_kind(s->kinds_mask, s->d.has_mix, HK_MAX_KINDS);
     s->n_materials = d->n_materials;
     HIP_TRY(s->materials.upload(dm.data(), dm.size() * sizeof(DMaterial)));
     return HK_OK;

@@ -13,7 +13,7 @@
 // before anything changes.  (hk_scene_rebuild_bvh waits once, for the size of the tree it built; it is also the one edit that changes
 // bvh_depth and n_nodes — what follows from that is argued at its entry point.)
 // Caches keyed by the scene that an edit must not invalidate, and why it does not: DScene::all_opaque and the HK_TRI_OPAQUE bits (opacity
-// class of every material and the medium interfaces are unchanged), kinds_mask (kinds unchanged), simple_lights / has_escape_lights
+// class of every material and the medium interfaces are unchanged), kinds_mask (a record changes its kind only to or from a Mix of kinds the mask has: check_material_update), simple_lights / has_escape_lights
 // (lights and textures unchanged), bvh_depth and n_nodes (topology unchanged), the light BVH (built from the base geometry, Q18),
 // the context's noted call (flushed) and lanes (joined); the integrator's path state is sized from those flags only.
 // hk_scene_update_lights changes the light set, so it re-derives what is derived from it, through hk_scene_create's own code path
@@ -205,11 +205,18 @@ int acquire_staging(hk_scene* s, size_t bytes, hk_scene::Staging*& st) {
     }
     return HK_OK;
 }
-// what an update may change: everything but the kind, a Mix's children, and the opacity class; indices must stay in range
+// what an update may change: everything but the kind, a Mix's children, and the opacity class; indices must stay in range.  The one
+// change of kind: a record may BECOME a MixMaterial of two materials of the scene, and a MixMaterial may become a material of a kind
+// the scene already shades (hk_scene::kinds_mask: the kinds of the non-Mix records at creation, which never shrinks) — a Mix resolves
+// to records of the scene, so neither direction brings a kind the scene's kernels and queues were not chosen for.
 std::string check_material_update(const hk_scene* s, int idx, const hk_material& old, const hk_material& m) {
     const std::string at = "hk_scene_update_materials: material " + std::to_string(idx) + ": ";
-    if (m.kind != old.kind) return at + "the kind differs from the record it replaces";
-    if (m.kind == HK_MAT_MIX && (m.i[0] != old.i[0] || m.i[1] != old.i[1] || std::memcmp(m.mix_key, old.mix_key, sizeof m.mix_key) != 0))
+    if (m.kind != old.kind) {
+        if (m.kind == HK_MAT_MIX) {
+            if (m.i[0] < 0 || m.i[0] >= s->n_materials || m.i[1] < 0 || m.i[1] >= s->n_materials) return at + "MixMaterial child material index out of range";
+        } else if (old.kind != HK_MAT_MIX || m.kind < 0 || m.kind >= 32 || !(s->kinds_mask & (1u << m.kind)))
+            return at + "the kind differs from the record it replaces";
+    } else if (m.kind == HK_MAT_MIX && (m.i[0] != old.i[0] || m.i[1] != old.i[1] || std::memcmp(m.mix_key, old.mix_key, sizeof m.mix_key) != 0))
         return at + "a MixMaterial's children (i[], mix_key) cannot change";
     for (int k = 0; k < 4; ++k)
         if (m.rgb[k].tex >= s->n_textures) return at + "rgb texture index out of range";
@@ -242,6 +249,8 @@ extern "C" int32_t hk_scene_update_materials(hk_scene* s, int32_t first, int32_t
     HIP_TRY(hipMemcpyAsync(s->materials.as<DMaterial>() + first, rec, bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipEventRecord(st->ev, c->stream));
     for (int j = 0; j < n; ++j) s->h_materials[first + j] = materials[j];
+    s->d.has_mix = hk::materials_have_kind(s->h_materials.data(), s->h_materials.size(), HK_MAT_MIX);   // which k_trace_lean the next call launches
+    s->d.single_kind = hk::single_material_kind(s->kinds_mask, s->d.has_mix, HK_MAX_KINDS);
     return HK_OK;
 }
 

@@ -353,6 +353,8 @@ struct DScene {
     // one line instead of five to six 64-byte sectors in four places (profiles/pmc_traffic_manylight.json: k_shade moved 2.4 x its algorithmic
     // bytes).  Same values, same arithmetic.  Null (HK_TRI_PACK=0): the separate arrays.
     const float* tri_shade;
+    int has_mix;                // a material record is a MixMaterial (hk_scene_create, hk_scene_update_materials): 0 selects the closest-hit kernel without the resolve
+    int single_kind;            // the kind of EVERY material record when they share one and none is a Mix (a launch constant of that kernel's flush), else -1
 };
 
 struct DTables {

@@ -382,7 +382,9 @@ int32_t hk_scene_destroy(hk_scene* scene);
  * hk_scene_update_materials: material records [first, first + n) of hk_scene_desc::materials are replaced by materials[0 .. n-1]
  * (upload through pinned memory owned by the scene).  Refused: a null pointer, n < 1 or a range outside the scene, and a record that
  * changes its kind, a Mix's children (i[0], i[1], mix_key), its opacity class (Matte with an alpha texture or alpha < 1) or names a
- * texture / spectrum index that is out of range.
+ * texture / spectrum index that is out of range.  ONE change of kind is accepted: a record may become a MixMaterial whose children are
+ * materials of the scene, and a MixMaterial may become a material of a kind that a non-Mix record of the scene had at hk_scene_create
+ * (either way the scene shades only kinds it was created for; whether it holds a Mix selects the closest-hit kernel of the next call).
  *
  * hk_scene_update_lights: light records [first, first + n) of hk_scene_desc::lights are replaced by lights[0 .. n-1].  Everything but
  * `kind` may change (spectrum, scale, position, direction, the spot matrices and cosines; v, normal, area, uv, Le, two_sided of an area
