@@ -55,6 +55,12 @@ inline int single_material_kind(unsigned kinds_mask, int has_mix, int max_kinds)
     while (!((kinds_mask >> k) & 1u)) ++k;
     return k < max_kinds ? k : -1;
 }
+// DPathState::shade_slot_walk from the knobs (ensure_state): HK_SHADE_SLOT_WALK, unless the emissive pre-scan is asked for
+// (HK_SHADE_PRESCAN=1: a pass over the kind queue) or the LEAN k_shade is off (HK_SHADE_LEAN=0) — both mean the queue walk.
+inline bool shade_slot_walk_wanted(bool slot_walk_knob, bool prescan, bool lean_knob) { return slot_walk_knob && !prescan && lean_knob; }
+// ... and per launch (launch_shade, for the LEAN k_shade of kind `kind`): the scene is of that one kind and the trace launch of this
+// bounce ran k_trace_lean's single-kind flush (launch_trace: not the counting instantiation), which marks escaped entries in mat_id.
+inline bool shade_slot_walk_launch(int wanted, int single_kind, int kind, bool single_flush) { return wanted != 0 && single_kind >= 0 && single_kind == kind && single_flush; }
 
 // Copies the 9 * n floats of triangles [first, first + n) to `dst` and, when `block` > 0, notes lo[3] hi[3] of every block of `block`
 // triangles the range touches in `fresh` (block first / block comes first).  false: a position is not finite (dst and fresh are then

@@ -978,9 +978,11 @@ __device__ __forceinline__ void trace_lean_body(const DPathState& st, const DSce
             int kind = -1;
             uint32_t eflag = 0u;   // HK_MATQ_EMISSIVE when the hit triangle carries an area light: travels in the kind-queue entry
             if (state == LR_ACTIVE && r.cur == DONE) {
-                if (r.best.prim < 0)
+                if (r.best.prim < 0) {
                     kind = -2;
-                else {
+                    // SINGLE: k_shade may walk the generation by slot instead of through the kind queue — the entry says that it holds no hit
+                    if constexpr (SINGLE) stream_st(reinterpret_cast<uint32_t*>(st.mat_id) + slot, HK_MAT_ESCAPED);
+                } else {
                     ++n_hits;
                     const DTriMeta hm = sc.meta[r.best.prim];
                     eflag = hm.arealight > 0 ? HK_MATQ_EMISSIVE : 0u;
@@ -2743,12 +2745,19 @@ __device__ __forceinline__ void lds_fetch4(const uint32_t* src, uint32_t* lds_wa
 __device__ __forceinline__ void lds_fetch16(const float4* src, float4* lds_wave_base) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
-template <int KIND, bool SIMPLE, bool FT, bool PRE, bool LEAN = false>
+// SLOTS (LEAN, a scene of ONE material kind whose trace launch ran the single-kind flush: launch_shade): the kind queue sorts nothing, so
+// the wave walks the segment's generation itself — slot = seg + i for i below the segment's RAY count — and every record load is a
+// contiguous 64-lane load.  An entry whose ray escaped holds HK_MAT_ESCAPED in mat_id and its lane sits the chunk out; the emissive flag is
+// mat_id's own bit.  The fetch-ahead needs no queue entry: the next chunk's slots are this chunk's + 64, requested near the top of a chunk,
+// behind the emission block (all lanes, escaped ones too: their successors may hold hits), the mat_id word with them in stage.entry[0 .. 255].  Shadow and continuing
+// records are appended in walk order, so every generation of a segment stays in ascending path-slot order down the bounces.
+template <int KIND, bool SIMPLE, bool FT, bool PRE, bool LEAN = false, bool SLOTS = false>
 __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& sc, const DTables& T, const DFrame& fr, const DSobol& sob, int depth, int first_kind, DStats* stats, const SegTickets& src,
                                            uint32_t* __restrict__ elist,   // elist: this wave's 128 LDS words (slots of flagged — emissive-hit — vertices waiting for the dense K8 pass)
                                            float* stash = nullptr,         // LEAN: the block's HK_SHADE_STASH * 256 LDS words
                                            ShadeStage stage = ShadeStage{}) {   // LEAN: the block's staging area of the fetch-ahead (null pointers: none)
     static_assert(!LEAN || (KIND == HK_MAT_MATTE && HK_LAMBDA_BY_SLOT), "the lean body is Matte's");
+    static_assert(!SLOTS || LEAN, "the slot walk is the lean body's");
     const int lane = lane_id();
     unsigned n_vertices = 0, n_lnodes = 0;
     unsigned nv_wave = 0;   // LEAN: the vertices of the whole wave
@@ -2766,7 +2775,7 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
     HK_FOR_EACH_SEGMENT_FROM(gw_v, st, src) {
     const int gw = uni(gw_v);
     const uint32_t* __restrict__ queue = st.mat_q + ((size_t)KIND * st.n_waves + gw) * st.wave_cap;
-    const int n = uni(*count_ptr(st, depth, Q_MAT0 + KIND, gw));
+    const int n = uni(*count_ptr(st, depth, SLOTS ? Q_RAY : Q_MAT0 + KIND, gw));   // SLOTS: every entry of the generation, hit or escaped
     const DPathGen g = gen_at(st, depth), gn = st.gen[(depth + 1) & 1];
     const size_t seg = (size_t)gw * st.wave_cap;
     const bool ones = depth == 0 && fr.implicit_ones;
@@ -2795,7 +2804,7 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
         if (lane < rest) elist[lane] = moved;
         n_emit = rest;
     };
-    const bool prescan = uni(st.shade_prescan) != 0;
+    const bool prescan = !SLOTS && uni(st.shade_prescan) != 0;
     if (prescan) {
         // HK_SHADE_PRESCAN=1 (A/B switch; films bit-identical): the flag is looked up in mat_id by a pass of its own over the whole
         // queue before the first vertex is shaded — two dependent round trips per chunk that the default does not make
@@ -2815,20 +2824,36 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
     // LEAN fetch-ahead: this wave's 64 entries of every staging part; the entry of chunk 1 is requested before chunk 0 starts
     const bool prefetch = LEAN && stage.entry != nullptr;
     const int wave0 = LEAN ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u)) : 0;
-    if constexpr (LEAN) {
+    if constexpr (LEAN && !SLOTS) {
         if (prefetch && 64 + lane < n) lds_fetch4(&queue[64 + lane], stage.entry + 256 + wave0);
     }
     for (int base = 0; base < n; base += 64) {
         int i = base + lane;
         bool active = i < n;
-        if constexpr (LEAN) {   // the entry of chunk k + 2 (never one at or past n): its address depends on nothing
+        if constexpr (LEAN && !SLOTS) {   // the entry of chunk k + 2 (never one at or past n): its address depends on nothing
             if (prefetch && i + 128 < n) lds_fetch4(&queue[i + 128], stage.entry + ((base >> 6) & 1) * 256 + wave0);
         }
-        const bool staged = prefetch && base > 0;   // this chunk's hit, ray_d and meta word were requested from the middle of the chunk before
-        uint32_t slot = active ? queue[i] : 0u;   // generation index of the path (the kind queue is a sorted subset of the segment)
+        const bool staged = prefetch && base > 0;   // this chunk's hit, ray_d and meta word were requested from the middle of the chunk before (SLOTS: from its top)
+        float4 H_staged = make_float4(0, 0, 0, 0), D_staged = H_staged;   // SLOTS: what the top of a staged chunk reads from the staging area
+        uint32_t meta_staged = 0;
+        uint32_t slot;
+        bool em_slot = false;
+        if constexpr (SLOTS) {
+            slot = (uint32_t)seg + (uint32_t)i;   // generation index of the path: the segment's entries in order
+            uint32_t mat_w = HK_MAT_ESCAPED;
+            if (staged) {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the staged records have landed
+                const uint32_t w = stage.entry[(int)threadIdx.x];
+                if (active) mat_w = w;
+            } else if (active)
+                mat_w = reinterpret_cast<const uint32_t*>(st.mat_id)[slot];
+            active = mat_w != HK_MAT_ESCAPED;
+            em_slot = active && (mat_w & HK_MAT_EMISSIVE_BIT) != 0u;
+        } else
+            slot = active ? queue[i] : 0u;   // generation index of the path (the kind queue is a sorted subset of the segment)
         {   // the entry's flag: an emissive hit waits in the list for the dense K8 pass (at most 63 waiting + 64 new of its 128 words)
-            const bool em = !prescan && (slot & HK_MATQ_EMISSIVE) != 0u;
-            slot &= ~HK_MATQ_EMISSIVE;
+            const bool em = SLOTS ? em_slot : !prescan && (slot & HK_MATQ_EMISSIVE) != 0u;
+            if constexpr (!SLOTS) slot &= ~HK_MATQ_EMISSIVE;
             const unsigned long long m = __ballot(em);
             if (m != 0ull) {
                 if (em) elist[n_emit + __popcll(m & ((1ull << lane) - 1ull))] = slot;
@@ -2836,9 +2861,25 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
                 if (n_emit >= 64) emit_pass(64);
             }
         }
+        if constexpr (SLOTS) {   // (behind the emission pass: nothing but the slot lives across it)
+            if (staged) {
+                const int t = (int)threadIdx.x;
+                H_staged = stage.hit[t], D_staged = stage.ray_d[t], meta_staged = stage.meta[t];
+                // the values are in registers before the staging area is handed to the next chunk's loads
+                asm volatile("" : "+v"(H_staged.x), "+v"(H_staged.y), "+v"(H_staged.z), "+v"(H_staged.w), "+v"(D_staged.x), "+v"(D_staged.y), "+v"(D_staged.z), "+v"(D_staged.w), "+v"(meta_staged) : : "memory");
+            }
+            if (prefetch && i + 64 < n) {   // the records of chunk k + 1 (never one at or past n), whatever became of this lane's own ray
+                const uint32_t ns = slot + 64u;
+                lds_fetch4(reinterpret_cast<const uint32_t*>(st.mat_id) + ns, stage.entry + wave0);
+                lds_fetch16(&st.hit[ns], stage.hit + wave0);
+                lds_fetch16(&g.ray_d[ns], stage.ray_d + wave0);
+                lds_fetch4(reinterpret_cast<const uint32_t*>(g.meta) + ns, stage.meta + wave0);
+            }
+        }
         bool push_shadow = false, push_ray = false;
         // state shared by the two halves of the vertex (NEE, then BSDF sampling): loaded once
         float4 H = make_float4(0, 0, 0, 0);
+        if constexpr (SLOTS) H = H_staged;
         Surface sf;
         v3 wo = mk3(0, 0, 1);
         DTriMeta meta{0u, 0u, 0u};
@@ -2860,12 +2901,15 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
         float4 shO = make_float4(0, 0, 0, 0), shD = shO;
         S4 shLd = s4(0.0f);
         W shRu{}, shRl{};
-        if constexpr (LEAN) nv_wave += (unsigned)(n - base < 64 ? n - base : 64);   // (wave-uniform: a scalar register)
+        if constexpr (SLOTS) nv_wave += (unsigned)__popcll(__ballot(active));   // (the entries that hold a hit)
+        else if constexpr (LEAN) nv_wave += (unsigned)(n - base < 64 ? n - base : 64);   // (wave-uniform: a scalar register)
         if (active) {
             if constexpr (!LEAN) ++n_vertices;
             float4 D;
             uint32_t meta_w = 0;   // LEAN: the record's 32-bit meta word (path slot, specular and any-non-specular bits)
-            if (LEAN && staged) {
+            if (SLOTS && staged)
+                D = D_staged, meta_w = meta_staged;   // (and H: read at the top of the chunk)
+            else if (LEAN && staged) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the staged records have landed
                 const int t = (int)threadIdx.x;
                 H = stage.hit[t], D = stage.ray_d[t], meta_w = stage.meta[t];
@@ -2968,7 +3012,7 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
                 sp[10 * 256] = beta.x, sp[11 * 256] = beta.y, sp[12 * 256] = beta.z, sp[13 * 256] = beta.w;
                 sp[14 * 256] = __uint_as_float(meta_w);
                 // the registers are at their lowest here: the next chunk's entry (requested a chunk ago) names the records to stage
-                if (prefetch && i + 64 < n) {
+                if (!SLOTS && prefetch && i + 64 < n) {
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the entry has landed
                     const uint32_t ns = stage.entry[(((base >> 6) + 1) & 1) * 256 + (int)threadIdx.x] & ~HK_MATQ_EMISSIVE;
                     lds_fetch16(&st.hit[ns], stage.hit + wave0);
@@ -3159,7 +3203,7 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
     wave_add(&stats->vertices, n_vertices);
     wave_add(&stats->light_nodes, n_lnodes);
 }
-template <int KIND, bool SIMPLE = false, bool FT = false, bool PRE = false, bool LEAN = false>
+template <int KIND, bool SIMPLE = false, bool FT = false, bool PRE = false, bool LEAN = false, bool SLOTS = false>
 __global__ void __attribute__((amdgpu_flat_work_group_size(256, 256), amdgpu_waves_per_eu(LEAN ? (FT ? HK_SHADE_WAVES_LEAN : HK_SHADE_WAVES_LEAN_HASH) : ShadeWaves<KIND>::value))) k_shade(DPathState st, DScene sc, DTables T, DFrame fr, DSobol sob, int depth, int first_kind, DStats* stats) {
     __shared__ uint32_t emit_list[4 * 128];
     SegTickets src = seg_open(st, ticket_ptr(st, depth, TK_SHADE0 + KIND), st.dynamic_segments != 0, depth, Q_MAT0 + KIND);
@@ -3173,7 +3217,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256, 256), amdgpu_wav
         __shared__ uint32_t stage_meta[256];
         ShadeStage stage{};
         if (st.shade_prefetch) stage.entry = stage_entry, stage.hit = stage_hit, stage.ray_d = stage_ray_d, stage.meta = stage_meta;
-        shade_body<KIND, SIMPLE, FT, PRE, true>(st, sc, T, fr, sob, depth, first_kind, stats, src, emit_list + (threadIdx.x >> 6) * 128, stash, stage);
+        shade_body<KIND, SIMPLE, FT, PRE, true, SLOTS>(st, sc, T, fr, sob, depth, first_kind, stats, src, emit_list + (threadIdx.x >> 6) * 128, stash, stage);
     } else
         shade_body<KIND, SIMPLE, FT, PRE>(st, sc, T, fr, sob, depth, first_kind, stats, src, emit_list + (threadIdx.x >> 6) * 128);
 }

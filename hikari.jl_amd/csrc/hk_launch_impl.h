@@ -156,12 +156,13 @@ static void lean_dispatch(const DScene& sc, const DFrame& fr, F&& launch) {
         });
     });
 }
+// The flush of k_trace_lean's instantiation follows the scene's materials (DScene::has_mix / single_kind, kept current by
+// hk_scene_update_materials): 0 with the MixMaterial resolve, 1 without it, 2 without it and for ONE material kind.  The counting
+// instantiations (count_nodes, a diagnostic) are not multiplied: they keep the general flush.
+static int lean_flush(const DScene& sc, const DFrame& fr) { return (sc.has_mix || fr.count_nodes) ? 0 : (HK_TRACE_SINGLE_KIND && sc.single_kind >= 0 ? 2 : 1); }
 void launch_trace(hipStream_t s, int n_cu, const DPathState& st, const DScene& sc, const DTables& T, const DFrame& fr, int depth, DStats* stats) {
     if (lean_scene(sc)) {
-        // The flush of the instantiation follows the scene's materials (DScene::has_mix / single_kind, kept current by
-        // hk_scene_update_materials): 0 with the MixMaterial resolve, 1 without it, 2 without it and for ONE material kind.  The counting
-        // instantiations (count_nodes, a diagnostic) are not multiplied: they keep the general flush.
-        const int flush = sc.has_mix ? 0 : (HK_TRACE_SINGLE_KIND && sc.single_kind >= 0 ? 2 : 1);
+        const int flush = lean_flush(sc, fr);
         lean_dispatch<1024, 1536, HK_TRACE_NC32>(sc, fr, [&](auto COUNT, auto STACK, auto BLOCK, auto NC, auto QN) {
             constexpr int block = decltype(BLOCK)::value;
             constexpr bool count = decltype(COUNT)::value;
@@ -305,7 +306,14 @@ void launch_shade(hipStream_t s, int n_cu, int kind, const DPathState& st, const
     // the LEAN instantiation — those facts at compile time, the second half's values handed over through LDS, five waves per SIMD
     // (HK_SHADE_LEAN=0: the general instantiation; A/B switch, films bit-identical)
     if (kind == HK_MAT_MATTE && sc.simple_lights && lean_scene(sc) && st.compact && st.meta32 && st.sh_final && !preselect_lights(sc, st) && knob_on("HK_SHADE_LEAN")) {
-        with_bool(ft, [&](auto FT) { launch_resident<k_shade<HK_MAT_MATTE, true, decltype(FT)::value, false, true>>(s, n_cu, st, 256, 8, sc, T, fr, sob, depth, first_kind, stats); });
+        // ... and by slot instead of through the kind queue where the scene is all Matte and this bounce's trace launch marked the escaped
+        // entries (the single-kind flush); decided per launch: hk_scene_update_materials changes single_kind (HK_SHADE_SLOT_WALK=0: never)
+        const bool slots = shade_slot_walk_launch(st.shade_slot_walk, sc.single_kind, kind, lean_flush(sc, fr) == 2);
+        with_bool(ft, [&](auto FT) {
+            with_bool(slots, [&](auto SLOTS) {
+                launch_resident<k_shade<HK_MAT_MATTE, true, decltype(FT)::value, false, true, decltype(SLOTS)::value>>(s, n_cu, st, 256, 8, sc, T, fr, sob, depth, first_kind, stats);
+            });
+        });
         return;
     }
     // the kinds with next-event instantiations of their own (table-only draws, a light chosen beforehand); the others run k_shade<KIND>

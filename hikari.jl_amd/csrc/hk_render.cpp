@@ -272,6 +272,8 @@ int ensure_state(hk_integrator* I, int capacity, const PassTraits& t, hipStream_
     // HK_SHADE_PRESCAN=1: k_shade looks a segment's emissive hits up in mat_id before its first vertex, as it did before the flag travelled in the kind-queue entry (A/B switch, films bit-identical)
     I->st.shade_prescan = hk::knob_int("HK_SHADE_PRESCAN", 0) != 0 ? 1 : 0;
     I->st.shade_prefetch = hk::knob_on("HK_SHADE_PREFETCH") ? 1 : 0;   // 0: the LEAN k_shade loads every chunk's records directly (A/B switch, films bit-identical)
+    // 0, or HK_SHADE_PRESCAN=1 / HK_SHADE_LEAN=0: the LEAN k_shade of a single-kind scene walks the kind queue, not the generation by slot (A/B switch, films bit-identical)
+    I->st.shade_slot_walk = hk::shade_slot_walk_wanted(hk::knob_on("HK_SHADE_SLOT_WALK"), I->st.shade_prescan != 0, hk::knob_on("HK_SHADE_LEAN")) ? 1 : 0;
     I->st.ticket_share = hk::knob_int("HK_TICKET_SHARE", 1) ? 1 : 0;
     {   // a SMALL pass (at most 16 chunks for each of 4 waves per CU: a one-sample call at 800^2) hands segment g to wave g of every launch
         // (static stride where a grid is smaller): the 17 k_segment_lists launches of a call and the ticket round trips go, and the segment

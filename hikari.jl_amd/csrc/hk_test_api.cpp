@@ -195,7 +195,9 @@ extern "C" int32_t hk_test_medium_bricks(hk_scene* s, int32_t idx, int32_t* dims
 
 extern "C" int32_t hk_test_queue_counts(hk_integrator* I, int32_t depth, int32_t kind, int32_t* n_segments, int32_t* counts, int32_t* flagged) {
     if (!I || !n_segments) return fail(HK_ERR_INVALID, "hk_test_queue_counts: null argument");
-    if (kind < 0 || kind >= HK_MAX_KINDS || depth < 0 || depth >= I->st_depth + 2) return fail(HK_ERR_INVALID, "hk_test_queue_counts: kind or depth out of range");
+    if (kind < -2 || kind >= HK_MAX_KINDS || depth < 0 || depth >= I->st_depth + 2) return fail(HK_ERR_INVALID, "hk_test_queue_counts: kind or depth out of range");
+    if (kind < 0 && flagged) return fail(HK_ERR_INVALID, "hk_test_queue_counts: only a kind's queue has flagged entries");
+    const int queue = kind == -1 ? Q_RAY : (kind == -2 ? Q_ESCAPED : Q_MAT0 + kind);   // -1: the generation's rays, -2: those that escaped
     if (!I->st.counters) return fail(HK_ERR_INVALID, "hk_test_queue_counts: no pass has been rendered");
     *n_segments = I->st.n_waves;
     if (!counts) return HK_OK;
@@ -204,7 +206,7 @@ extern "C" int32_t hk_test_queue_counts(hk_integrator* I, int32_t depth, int32_t
     KnobScope knobs(&c->knobs);
     if (int e = join_lanes(c)) return e;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(counts, I->st.counters + (size_t)(depth * Q_COUNT + Q_MAT0 + kind) * I->st.n_waves, (size_t)I->st.n_waves * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(counts, I->st.counters + (size_t)(depth * Q_COUNT + queue) * I->st.n_waves, (size_t)I->st.n_waves * sizeof(int), hipMemcpyDeviceToHost));
     if (!flagged) return HK_OK;
     // the entries themselves (the kind's queue is overwritten by every bounce: they are those of the bounce traced last)
     const size_t Q = (size_t)I->st.n_waves * I->st.wave_cap;

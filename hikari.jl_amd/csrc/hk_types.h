@@ -50,6 +50,7 @@ struct DNode {
 };
 
 #define HK_MAT_EMISSIVE_BIT 0x40000000   // DPathState::mat_id: the hit triangle carries an area light (set by the trace kernels)
+#define HK_MAT_ESCAPED 0xffffffffu       // DPathState::mat_id: the ray of this entry hit nothing (k_trace_lean's single-kind flush; no material index is this large: k_shade's slot walk skips the entry)
 #define HK_MATQ_EMISSIVE 0x80000000u     // DPathState::mat_q: the same flag in the top bit of the kind-queue entry (a generation index is below 2^31: ensure_state)
 #define HK_TRI_OPAQUE 1u  // e1.w bit: surface is neither a medium transition nor alpha-tested
 
@@ -431,7 +432,7 @@ struct DPathState {
     int wave_cap;          // entries per wave segment (multiple of 64); W * wave_cap >= capacity
     DPathGen gen[2];       // gen[depth & 1]: the ray queue of that depth IS this array (no index queue)
     float4* hit;           // per entry of the current generation: t, prim(bits), u, v
-    int* mat_id;           // per entry of the current generation: resolved material index of the hit (| HK_MAT_EMISSIVE_BIT)
+    int* mat_id;           // per entry of the current generation: resolved material index of the hit (| HK_MAT_EMISSIVE_BIT); HK_MAT_ESCAPED where the single-kind flush of k_trace_lean saw the ray escape
     uint2* sel_light;      // per entry of the current generation: the next-event light k_light_select chose (1-based index, pmf bits); scenes without media
     // per path slot: written once by the camera kernel, accumulated into (L) along the path, read by the film kernel
     float4* lambda_s;
@@ -487,6 +488,7 @@ struct DPathState {
     int view_cache;
     int shade_prescan;     // 1 (HK_SHADE_PRESCAN=1; A/B switch, films bit-identical): k_shade finds a segment's emissive hits by a scan of mat_id before its first vertex instead of by the flag in the queue entry
     int shade_prefetch;    // 1 (HK_SHADE_PREFETCH=0: off; A/B switch, films bit-identical): the LEAN k_shade stages the next chunk's hit, ray_d and meta word in LDS by global->LDS loads
+    int shade_slot_walk;   // 1 (HK_SHADE_SLOT_WALK=0: off; A/B switch, films bit-identical): in a lean scene of one material kind the LEAN k_shade walks a segment's generation by slot, not through the kind queue (launch_shade decides per launch)
 };
 
 struct DStats {

@@ -744,7 +744,8 @@ int32_t hk_test_medium_bricks(hk_scene* scene, int32_t idx, int32_t* dims, float
    segment of the path state: *n_segments = the number of segments, counts (NULL: only *n_segments) = that many entry counts — what
    one wave of k_shade walked in 64-entry chunks.  flagged (NULL: not wanted; needs counts): per segment, how many of those entries carry
    the emissive flag — read from the queue itself, which every bounce overwrites, so `depth` must be the bounce traced last (a pass of
-   max_depth 1: depth 0).  Staged passes only (a pass rendered in one fused launch leaves no counts); waits for the context's stream. */
+   max_depth 1: depth 0).  kind -1: the rays of the generation at `depth` (hits and escaped together), kind -2: those of them that escaped
+   (both without `flagged`).  Staged passes only (a pass rendered in one fused launch leaves no counts); waits for the context's stream. */
 int32_t hk_test_queue_counts(hk_integrator* integrator, int32_t depth, int32_t kind, int32_t* n_segments, int32_t* counts, int32_t* flagged);
 
 #ifdef __cplusplus
