@@ -478,8 +478,8 @@ struct DPathState {
     // k_camera and fetched by the depth-0 traversal and shading).  Independently of both, the COMPACT layouts keep r_l — one float — in the
     // unused fourth word of ray_d instead of an array of its own.
     int meta32, const_origin;
-    int sh_final;          // 1 (opaque scenes without media): slim shadow records — sh_d.w holds the denominator average(w_u + w_l) of the contribution, the two weights are not stored (hk_kernels.hip: shadow_contribute_final)
-    // THE CAMERA GENERATION: what k_camera writes and every depth-0 reader reads (gen_at in hk_kernels.hip).  view_cache 0: it IS gen[0]
+    int sh_final;          // 1 (opaque scenes without media): slim shadow records — sh_d.w holds the denominator average(w_u + w_l) of the contribution, the two weights are not stored (hk_shadow.h: shadow_contribute_final)
+    // THE CAMERA GENERATION: what k_camera writes and every depth-0 reader reads (gen_at in hk_wave_queues.h).  view_cache 0: it IS gen[0]
     // (the same pointers), which depth 1 overwrites with its continuing records.  view_cache 1 (lean records, a one-pass frame on the
     // integrator's own set; hk_render.cpp: view cache): a third record set — ray_o, ray_d and the 4-byte meta word — that no bounce
     // writes, so a pass whose camera records would be the previous pass's, value for value, does not launch k_camera; k_film then

@@ -237,12 +237,12 @@ def _strips(n, x0, y):
 
 
 def test_deep_tree_recoloured_and_moved_equals_fresh(hk, gpu_ctx):
-    """hk::preselect_lights is true from HK_PRESELECT_MIN = 64 lights in the tree (hk_kernels.hip; no media): k_light_select then
+    """hk::preselect_lights is true from HK_PRESELECT_MIN = 64 lights in the tree (hk_shade.h; no media): k_light_select then
     chooses the next-event light.  64 emissive triangles in two meshes (40 + 24, so the moved lights are a contiguous run that is not
     the whole set); every third emitter re-coloured, the second mesh moved with its lights."""
     from hikari_jl_amd import lights as LT
     from hikari_jl_amd.geometry import Mesh
-    src = open(os.path.join(ROOT, "hikari.jl_amd", "csrc", "hk_kernels.hip")).read()
+    src = open(os.path.join(ROOT, "hikari.jl_amd", "csrc", "hk_shade.h")).read()
     assert re.search(r"#define HK_PRESELECT_MIN (\d+)", src).group(1) == "64"
     em = lambda: hk.MediumInterface(hk.MatteMaterial(Kd=hk.RGBSpectrum(0.0)), emission=hk.Emissive(Le=hk.RGBSpectrum(5.0), scale=1.0, two_sided=True))
     A_, B_ = _strips(40, -0.95, 1.9), _strips(24, -0.6, 1.6)

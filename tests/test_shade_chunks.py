@@ -1,4 +1,4 @@
-"""How k_shade finds the emissive hits of a segment (hk_kernels.hip: shade_body).  The trace kernels put the flag "this hit sits on an
+"""How k_shade finds the emissive hits of a segment (hk_shade.h: shade_body).  The trace kernels put the flag "this hit sits on an
 area light" into the top bit of the kind-queue entry (HK_MATQ_EMISSIVE); the shading wave gathers the flagged entries from the queue
 load its main pass makes anyway and runs the dense emission pass whenever 64 of them wait, and once more after the segment's last
 chunk.  HK_SHADE_PRESCAN=1 brings back the scan of mat_id over the whole queue before the first vertex.  Either way the same additions

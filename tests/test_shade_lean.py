@@ -1,4 +1,4 @@
-"""The LEAN instantiation of k_shade<Matte> (hk_kernels.hip: shade_body): in a lean scene (all surfaces opaque, no media) whose state
+"""The LEAN instantiation of k_shade<Matte> (hk_shade.h: shade_body): in a lean scene (all surfaces opaque, no media) whose state
 holds the lean records, the record layouts, r_u == 1 and "no medium" are compile-time facts, the values of a vertex's second half wait
 in LDS while the light is sampled, and the kernel runs at five waves per SIMD.  Every step only removes operations whose result is fixed
 or moves values, so each case below is rendered at the default and under HK_SHADE_LEAN=0 (the general instantiation) and compared bit for

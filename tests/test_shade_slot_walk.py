@@ -1,4 +1,4 @@
-"""k_shade's slot walk (hk_kernels.hip: shade_body<.., LEAN, SLOTS>).  In a lean scene whose material records are all of one kind the
+"""k_shade's slot walk (hk_shade.h: shade_body<.., LEAN, SLOTS>).  In a lean scene whose material records are all of one kind the
 kind queue sorts nothing: the LEAN k_shade walks a segment's generation itself, slot = seg + i for every ray of the generation, and
 skips the entries whose ray escaped — the single-kind flush of k_trace_lean leaves HK_MAT_ESCAPED in their mat_id word.  Per path
 nothing changes, only the order in which a wave meets its vertices; so every case is rendered five ways — the default (slot walk),
