@@ -150,7 +150,7 @@ EXPORTED_SYMBOLS = [
     "hk_film_pin_host", "hk_film_unpin_host", "hk_scene_set_transform", "hk_scene_update_materials", "hk_scene_update_lights", "hk_scene_update_envmap",
     "hk_film_update_aux", "hk_film_read_aux", "hk_film_present", "hk_film_present_async",
     "hk_scene_update_medium", "hk_scene_medium_copy", "hk_test_medium_bricks", "hk_scene_set_vertices", "hk_scene_bvh_cost", "hk_scene_bvh_copy",
-    "hk_scene_bvh_leaves", "hk_scene_rebuild_bvh", "hk_test_queue_counts", "hk_scene_update_medium_dense", "hk_scene_medium_tree_copy",
+    "hk_scene_bvh_leaves", "hk_scene_rebuild_bvh", "hk_test_queue_counts", "hk_test_tri_geo", "hk_scene_update_medium_dense", "hk_scene_medium_tree_copy",
 ]
 
 # prototypes (argtypes, restype) of the geometry edit, the tree introspection and the dense-field medium update, in the header's order;

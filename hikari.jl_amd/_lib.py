@@ -89,6 +89,7 @@ def lib():
         "hk_scene_medium_copy": ([vp, i32, PI, PF, C.POINTER(C.c_uint32)], i32),
         "hk_test_medium_bricks": ([vp, i32, PI, PF], i32),
         "hk_test_queue_counts": ([vp, i32, i32, PI, PI, PI], i32),
+        "hk_test_tri_geo": ([vp, i32, PI, PI, PF], i32),
     }
     sig.update(A.PROTOTYPES)
     for name, (args, res) in sig.items():

@@ -1058,8 +1058,26 @@ HKD v2 uv_at(const DScene& sc, int prim, float w, float u, float v) {
     // default uvs (0,0),(1,0),(1,1)
     return mk2(w * 0.0f + u * 1.0f + v * 1.0f, w * 0.0f + u * 0.0f + v * 1.0f);
 }
+// THE GEOMETRIC NORMAL AND THE AREA OF A TRIANGLE, (n.x, n.y, n.z, area): a function of the three world positions alone.  This is the
+// one place that computes them — surface_at for a scene without the table, and every writer of the table (k_tri_geo at
+// hk_scene_create, k_xform_tris, k_set_tris: wherever positions are written), so a row holds the bits surface_at would compute (no
+// contraction, correctly rounded square root and division; a zero-area triangle gives the same NaNs).
+HKD float4 tri_geo_of(v3 a, v3 b, v3 c) {
+    v3 cr = cross(b - a, c - a);
+    v3 n = normalize(cr);
+    return make_float4(n.x, n.y, n.z, 0.5f * norm(cr));
+}
+// the table's row (DScene::tri_geo != 0): words 28 .. 31 of the packed record, else the float4 array behind the positions
+HKD float4 tri_geo_row(const DScene& sc, int prim) {
+    if (sc.tri_shade) return *reinterpret_cast<const float4*>(tri_record(sc, prim) + 28);
+    return reinterpret_cast<const float4*>(sc.positions + sc.tri_geo)[prim];
+}
 // Only the fields the BSDFs consume are produced: dpdu/dpdv/shading tangents feed the texture-filter
 // context, which texture evaluation ignores (textures/texture-ref.jl:126-135), so they are not computed.
+// GEO (the lean k_shade where the scene has the table and HK_TRI_GEO is on; launch_shade): the geometric normal and the area come from
+// the table's row — nothing else here needs the positions, pi = ro + rd * t.  A compile-time choice: with both arms behind a
+// run-time test every k_shade instantiation gained scratch (LAB_NOTEBOOK "tri_geo"), so the other callers compute as before.
+template <bool GEO = false>
 HKD Surface surface_at(const DScene& sc, int prim, float bu, float bv, v3 ro, v3 rd, float t) {
     Surface s;
     float w = 1.0f - bu - bv;
@@ -1067,21 +1085,31 @@ HKD Surface surface_at(const DScene& sc, int prim, float bu, float bv, v3 ro, v3
     // (only the shading and light-selection kernels read the packed record: in the traversal kernels the second address path cost
     // k_trace_lean 1.6 ms per Cornell frame without ever being taken, and scenes whose attributes fit in L2 gain nothing — hk_scene.cpp
     // builds the records for scenes of >= 32 768 triangles)
-    v3 a, b, c;
-    if (sc.tri_shade) {
-        const float* p = tri_record(sc, prim);
-        a = mk3(p[0], p[1], p[2]);
-        b = mk3(p[3], p[4], p[5]);
-        c = mk3(p[6], p[7], p[8]);
-        const float* q = p + 18;   // (a mesh without uvs: the record holds uv_at's defaults — the same products and sums)
-        s.uv = mk2(w * q[0] + bu * q[2] + bv * q[4], w * q[1] + bu * q[3] + bv * q[5]);
+    float4 g;
+    if constexpr (GEO) {
+        g = tri_geo_row(sc, prim);
+        if (sc.tri_shade) {
+            const float* q = tri_record(sc, prim) + 18;
+            s.uv = mk2(w * q[0] + bu * q[2] + bv * q[4], w * q[1] + bu * q[3] + bv * q[5]);
+        } else
+            s.uv = uv_at(sc, prim, w, bu, bv);
     } else {
-        tri_vertices(sc, prim, a, b, c);
-        s.uv = uv_at(sc, prim, w, bu, bv);
+        v3 a, b, c;
+        if (sc.tri_shade) {
+            const float* p = tri_record(sc, prim);
+            a = mk3(p[0], p[1], p[2]);
+            b = mk3(p[3], p[4], p[5]);
+            c = mk3(p[6], p[7], p[8]);
+            const float* q = p + 18;   // (a mesh without uvs: the record holds uv_at's defaults — the same products and sums)
+            s.uv = mk2(w * q[0] + bu * q[2] + bv * q[4], w * q[1] + bu * q[3] + bv * q[5]);
+        } else {
+            tri_vertices(sc, prim, a, b, c);
+            s.uv = uv_at(sc, prim, w, bu, bv);
+        }
+        g = tri_geo_of(a, b, c);
     }
-    v3 cr = cross(b - a, c - a);
-    v3 n = normalize(cr);
-    s.area = 0.5f * norm(cr);
+    v3 n = mk3(g.x, g.y, g.z);
+    s.area = g.w;
     v3 ns = n;
     if (sc.tri_shade || sc.normals) {   // (a packed record of a mesh without vertex normals holds NaNs)
         // the nine floats in three loads up front: read field by field behind the NaN test they become twelve per-lane loads

@@ -107,6 +107,23 @@ inline void merge_block_boxes(std::vector<float>& block_box, int n_tris, int fir
     }
 }
 
+// THE GEOMETRY TABLE (DScene::tri_geo, hk_types.h).  tri_geo_word: the value of that word for a scene as created — 0 no table (no
+// triangles, or rows that an int offset cannot reach), 1 the rows are words 28 .. 31 of the packed records, else the offset in floats of
+// the float4 rows from the start of the positions: the first 16-byte boundary behind the 9 n_tris floats.  positions_floats: what the
+// positions' allocation holds then.
+inline int tri_geo_word(int n_tris, bool packed) {
+    if (n_tris <= 0) return 0;
+    if (packed) return 1;
+    const long long off = (9LL * n_tris + 3) & ~3LL;
+    return off <= 0x7fffffffLL ? (int)off : 0;
+}
+inline size_t positions_floats(int n_tris, int word, bool packed) {
+    const size_t T = n_tris > 0 ? (size_t)n_tris : 0;
+    return (!packed && word != 0) ? (size_t)word + 4 * T : 9 * T;
+}
+// K12 per launch (launch_film): the grouped fold is the arm of passes of 64 k samples per pixel (HK_FILM_FOLD=0: never)
+inline bool film_fold_launch(bool knob, int samples_in_pass) { return knob && samples_in_pass >= 64 && (samples_in_pass & 63) == 0; }
+
 // hk_scene_bvh_cost's formula over a whole tree on the host: node(i, lo, hi, c0, c1) hands out node i (node 0 is the root); the terms
 // are added in node order.  0 for a tree without inner nodes or a root without area.
 template <class Node>

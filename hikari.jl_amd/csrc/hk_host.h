@@ -261,6 +261,7 @@ struct hk_scene {
     int n_textures = 0, n_spectra = 0;
     std::vector<int> level_start;           // breadth-first node levels: level L is [level_start[L], level_start[L + 1])
     DevBuf base_pos, base_nrm, base_tan, slot_of_prim;   // base geometry (as created / last hk_scene_set_vertices) and the leaf slot of every triangle (first transform or new vertices)
+    int tri_geo = 0;                        // DScene::tri_geo as created (upload_attributes): where the geometry table's rows are
     DevBuf vertex_stage;                    // hk_scene_set_vertices: the uploaded range and its interval table, read by k_set_tris (grows with the largest range)
     DevBuf cost_partial;                    // hk_scene_bvh_cost: the per-block sums of k_bvh_cost (first call)
     double cost_created = 0.0;              // the tree cost of the tree as built (hk_scene_bvh_cost)

@@ -2357,9 +2357,26 @@ __device__ inline void xform_dir(const float* M, int stride, const float* in, fl
     for (int k = 0; k < 3; ++k) out[k] = r[k] / len;
 }
 
+// THE PER-TRIANGLE GEOMETRY TABLE (DScene::tri_geo): a row is written by whoever writes the triangle's positions — k_tri_geo for a
+// whole scene at hk_scene_create, k_xform_tris and k_set_tris for the rows they rewrite — through tri_geo_of, the function surface_at
+// itself calls in a scene without the table.  geo: the float4 array behind the positions; a scene with packed records (shade) keeps
+// the row in words 28 .. 31 of the record.  A BVH refit or rebuild moves no vertex and writes no row.
+__device__ inline void tri_geo_store(const float* p, size_t t, float4* __restrict__ geo, float* __restrict__ shade) {
+    const float4 g = tri_geo_of(mk3(p[0], p[1], p[2]), mk3(p[3], p[4], p[5]), mk3(p[6], p[7], p[8]));
+    if (shade) *reinterpret_cast<float4*>(shade + 32 * t + 28) = g;
+    else if (geo) geo[t] = g;
+}
+__global__ void __launch_bounds__(256) k_tri_geo(const float* __restrict__ pos, int n, float4* __restrict__ geo, float* __restrict__ shade) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        float p[9];
+        for (int j = 0; j < 9; ++j) p[j] = pos[9 * (size_t)i + j];
+        tri_geo_store(p, (size_t)i, geo, shade);
+    }
+}
+
 __global__ void __launch_bounds__(256) k_xform_tris(DXform X, int first, int n, const float* __restrict__ bp, const float* __restrict__ bn, const float* __restrict__ bt,
                                                     const int* __restrict__ slot_of_prim, float* __restrict__ pos, float* __restrict__ nrm, float* __restrict__ tan,
-                                                    float* __restrict__ shade, float4* __restrict__ leaf) {
+                                                    float* __restrict__ shade, float4* __restrict__ geo, float4* __restrict__ leaf) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const size_t t = (size_t)first + i;
         float p[9];
@@ -2371,6 +2388,7 @@ __global__ void __launch_bounds__(256) k_xform_tris(DXform X, int first, int n, 
         for (int j = 0; j < 9; ++j) pos[9 * t + j] = p[j];
         if (shade)
             for (int j = 0; j < 9; ++j) shade[32 * t + j] = p[j];
+        tri_geo_store(p, t, geo, shade);
         if (nrm) {
             float q[9];
             for (int v = 0; v < 3; ++v) {
@@ -2522,7 +2540,7 @@ __global__ void __launch_bounds__(256) k_set_tris(DSetTris A) {
         float uv[6];
         if (A.in_uv) wave_rows_load<6>(A.in_uv + 6 * r0, rows, lds, lane, A.uvs + 6 * t0, uv);   // not transformed: the copy is the array
         if (!live) continue;
-        if (A.shade) {   // p[9] n[9] uv[6] meta[3] pad[5]
+        if (A.shade) {   // p[9] n[9] uv[6] meta[3] pad[1] geo[4] (the geometry row: tri_geo_store below)
             float* S = A.shade + 32 * t;
             float4* S4 = reinterpret_cast<float4*>(S);
             S4[0] = make_float4(p[0], p[1], p[2], p[3]);
@@ -2536,6 +2554,7 @@ __global__ void __launch_bounds__(256) k_set_tris(DSetTris A) {
             if (A.in_uv)
                 for (int j = 0; j < 3; ++j) *reinterpret_cast<float2*>(S + 18 + 2 * j) = make_float2(uv[2 * j], uv[2 * j + 1]);
         }
+        tri_geo_store(p, t, A.geo, A.shade);
         float4* L = A.leaf + 3 * (size_t)A.slot_of_prim[t];
         hk_pack_leaf_tri(L, p, L[0].w, L[1].w, L[2].w);
     }

@@ -47,8 +47,10 @@ template <class Layout> void launch_postprocess(hipStream_t s, const hk_postproc
 void launch_atrous(hipStream_t s, const hk_denoise_params& P, int step, PlanarPixels src, const float* variance, PlanarPixels dst, int h, int w);
 void launch_atrous(hipStream_t s, const hk_denoise_params& P, int step, PackedPixels src, const float* variance, PackedPixels dst, float* out, const hk_postprocess_params* pp, int h, int w);
 void launch_slot_of_prim(hipStream_t s, const float4* leaf, int n, int* slot_of_prim);
+// the geometry table of a whole scene (DScene::tri_geo: the float offset of its rows behind `pos`; shade: the packed records hold them instead)
+void launch_tri_geo(hipStream_t s, float* pos, int n, int tri_geo, float* shade);
 void launch_xform_tris(hipStream_t s, const DXform& X, int first, int n, const float* bp, const float* bn, const float* bt, const int* slot_of_prim, float* pos, float* nrm, float* tan, float* shade,
-                       float4* leaf);
+                       float4* geo, float4* leaf);
 void launch_refit_level(hipStream_t s, int begin, int end, DNode* nodes, DQNode* qnodes, const DQGrid& grid, const float4* leaf, const float* pos);
 // hk_scene_set_vertices: one pass over the uploaded range (base copies, transform, every copy of the geometry, leaf slots)
 void launch_set_tris(hipStream_t s, const DSetTris& A);
@@ -71,6 +73,8 @@ void launch_dense_emit(hipStream_t s, const DDense& D, const uint32_t count[3], 
 
 // ---- sub-kernel entry points of the parity tests (hk_test_kernels.h) ----
 void launch_test_trace(hipStream_t s, const DScene& sc, int n, const float* o, const float* d, const float* tmax, float* t, int* prim, float* uv);
+// hk_test_tri_geo: out[t] = the geometry table's row of triangle t (recompute 0) or tri_geo_of of its world positions (1)
+void launch_test_tri_geo(hipStream_t s, const DScene& sc, int recompute, float4* out);
 void launch_test_trace_lean(hipStream_t s, int n_cu, const DScene& sc, int anyhit, int n, const float* o, const float* d, const float* tmax, float* t, int* prim, float* uv);
 void launch_test_sobol(hipStream_t s, const DTables& T, const DSobol& sob, int n, const int* px, const int* py, const int* si, const int* dim, float* o1, float* o2);
 void launch_test_camera(hipStream_t s, const DTables& T, const DFilter& flt, const DCamera& cam, const DSobol& sob, int height, int n, const int* px, const int* py, const int* si, float* out);

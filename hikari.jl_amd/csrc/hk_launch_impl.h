@@ -242,6 +242,9 @@ void launch_segment_lists(hipStream_t s, const DPathState& st, int n, const int*
     }
     hipLaunchKernelGGL(k_segment_lists, dim3(n, HK_LIST_SPLIT), dim3(1024), 0, s, st, qs);
 }
+// The lean k_shade reads the geometric normal and the area of the hit triangle from the scene's table (DScene::tri_geo) where there is
+// one; HK_TRI_GEO=0 (A/B switch; films bit-identical): it computes them from the positions, as every other caller of surface_at does.
+static bool tri_geo_on(const DScene& sc) { return sc.tri_geo != 0 && knob_on("HK_TRI_GEO"); }
 void launch_medium(hipStream_t s, int n_cu, const DPathState& st, const DScene& sc, const DTables& T, const DFrame& fr, const DSobol& sob, int depth, DStats* stats) {
     {
         const int d = depth, q = Q_MEDIUM;
@@ -311,7 +314,9 @@ void launch_shade(hipStream_t s, int n_cu, int kind, const DPathState& st, const
         const bool slots = shade_slot_walk_launch(st.shade_slot_walk, sc.single_kind, kind, lean_flush(sc, fr) == 2);
         with_bool(ft, [&](auto FT) {
             with_bool(slots, [&](auto SLOTS) {
-                launch_resident<k_shade<HK_MAT_MATTE, true, decltype(FT)::value, false, true, decltype(SLOTS)::value>>(s, n_cu, st, 256, 8, sc, T, fr, sob, depth, first_kind, stats);
+                with_bool(tri_geo_on(sc), [&](auto GEO) {   // the geometric normal and the area from the scene's table (HK_TRI_GEO=0: from the positions)
+                    launch_resident<k_shade<HK_MAT_MATTE, true, decltype(FT)::value, false, true, decltype(SLOTS)::value, decltype(GEO)::value>>(s, n_cu, st, 256, 8, sc, T, fr, sob, depth, first_kind, stats);
+                });
             });
         });
         return;
@@ -384,10 +389,15 @@ bool launch_small_pass(hipStream_t s, int n_cu, const DPathState& st, const DSce
 }
 void launch_film(hipStream_t s, const DPathState& st, const DFrame& fr, const DTables& T, void* accum, bool f64) {
     int g = grid_for(fr.n_pixels_padded >> 6, 4, 4096);   // one wave per 8x8 tile
-    if (f64)
-        hipLaunchKernelGGL(k_film<double>, dim3(g), dim3(256), 0, s, st, fr, T, (double*)accum);
-    else
-        hipLaunchKernelGGL(k_film<float>, dim3(g), dim3(256), 0, s, st, fr, T, (float*)accum);
+    // the grouped fold's arm is that of passes of 64 k samples; every other pass keeps the one-pixel kernel and its 4 KB of LDS
+    // (HK_FILM_FOLD=0: always the one-pixel kernel; A/B switch, films bit-identical)
+    const bool fold = film_fold_launch(knob_on("HK_FILM_FOLD"), fr.samples_in_pass);
+    if (f64) {   // (double accumulators keep the one-pixel kernel: grouped it takes 70 registers and loses a wave per SIMD)
+        hipLaunchKernelGGL((k_film<double, 1>), dim3(g), dim3(256), 0, s, st, fr, T, (double*)accum);
+    } else {
+        if (fold) hipLaunchKernelGGL((k_film<float, HK_FILM_FOLD_G>), dim3(g), dim3(256), 0, s, st, fr, T, (float*)accum);
+        else hipLaunchKernelGGL((k_film<float, 1>), dim3(g), dim3(256), 0, s, st, fr, T, (float*)accum);
+    }
 }
 void launch_sobol_table(hipStream_t s, const DSobol& sob, const DFrame& fr, uint2* table, int rows) {
     hipLaunchKernelGGL(k_sobol_table, dim3(grid_for((long)rows * fr.n_pixels_padded > 0x3fffffff ? 0x3fffffff : rows * fr.n_pixels_padded, 256, 8192)), dim3(256), 0, s, sob, fr, table, rows);
@@ -439,9 +449,12 @@ void launch_atrous(hipStream_t s, const hk_denoise_params& P, int step, PackedPi
 void launch_slot_of_prim(hipStream_t s, const float4* leaf, int n, int* slot_of_prim) {
     hipLaunchKernelGGL(k_slot_of_prim, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, leaf, n, slot_of_prim);
 }
+void launch_tri_geo(hipStream_t s, float* pos, int n, int tri_geo, float* shade) {
+    if (n > 0) hipLaunchKernelGGL(k_tri_geo, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, pos, n, tri_geo_rows(pos, tri_geo), shade);
+}
 void launch_xform_tris(hipStream_t s, const DXform& X, int first, int n, const float* bp, const float* bn, const float* bt, const int* slot_of_prim, float* pos, float* nrm,
-                       float* tan, float* shade, float4* leaf) {
-    hipLaunchKernelGGL(k_xform_tris, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, X, first, n, bp, bn, bt, slot_of_prim, pos, nrm, tan, shade, leaf);
+                       float* tan, float* shade, float4* geo, float4* leaf) {
+    hipLaunchKernelGGL(k_xform_tris, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, X, first, n, bp, bn, bt, slot_of_prim, pos, nrm, tan, shade, geo, leaf);
 }
 void launch_refit_level(hipStream_t s, int begin, int end, DNode* nodes, DQNode* qnodes, const DQGrid& grid, const float4* leaf, const float* pos) {
     hipLaunchKernelGGL(k_refit_level, dim3(grid_for(end - begin, 256, 8192)), dim3(256), 0, s, begin, end, nodes, qnodes, grid, leaf, pos);

@@ -268,7 +268,13 @@ int upload_bvh(hk_scene* s, const hk_scene_desc* d, const std::vector<uint8_t>& 
 
 int upload_attributes(hk_scene* s, const hk_scene_desc* d) {
     const int T = d->n_triangles;
-    HIP_TRY(s->positions.upload(d->positions, (size_t)T * 9 * 4));
+    // the geometry table (DScene::tri_geo) lives behind the positions, in their allocation: 16 B per triangle, filled on the device by
+    // hk_scene_create (a scene with packed records keeps the rows in the records and needs no room here)
+    bool tri_pack = T >= 32768;
+    if (const char* e = hk::knob("HK_TRI_PACK")) tri_pack = T > 0 && std::atoi(e) != 0;
+    s->tri_geo = hk::tri_geo_word(T, tri_pack);
+    HIP_TRY(s->positions.alloc(T > 0 ? hk::positions_floats(T, s->tri_geo, tri_pack) * 4 : 4));
+    if (T > 0) HIP_TRY(hipMemcpy(s->positions.p, d->positions, (size_t)T * 9 * 4, hipMemcpyHostToDevice));
     if (d->normals) HIP_TRY(s->normals.upload(d->normals, (size_t)T * 9 * 4));
     if (d->uvs) HIP_TRY(s->uvs.upload(d->uvs, (size_t)T * 6 * 4));
     if (d->tangents) HIP_TRY(s->tangents.upload(d->tangents, (size_t)T * 9 * 4));
@@ -276,9 +282,7 @@ int upload_attributes(hk_scene* s, const hk_scene_desc* d) {
     HIP_TRY(s->meta.upload(d->meta, (size_t)T * sizeof(hk_tri_meta)));
     // scenes whose attribute arrays (108 B per triangle) fit in an XCD's L2 gain nothing and pay the second address path (cloud config,
     // 24 triangles: shade + 4 %): records from 32 768 triangles up.  HK_TRI_PACK=0: never, 1: always (A/B switch and tests; films bit-identical)
-    bool tri_pack = T >= 32768;
-    if (const char* e = hk::knob("HK_TRI_PACK")) tri_pack = T > 0 && std::atoi(e) != 0;
-    if (tri_pack) {   // packed shading records (DScene::tri_shade): p[9] n[9] uv[6] meta[3] pad[5] per triangle, one 128-byte line
+    if (tri_pack) {   // packed shading records (DScene::tri_shade): p[9] n[9] uv[6] meta[3] pad[1] geo[4] per triangle, one 128-byte line
         std::vector<float> rec((size_t)T * 32, 0.0f);
         const float nan = std::numeric_limits<float>::quiet_NaN();
         static const float default_uv[6] = {0.0f, 0.0f, 1.0f, 0.0f, 1.0f, 1.0f};   // (0,0), (1,0), (1,1): uv_at's defaults
@@ -707,7 +711,7 @@ void fill_dscene(hk_scene* s, const hk_scene_desc* d, const BvhUpload& bvh, bool
     D.root_ref = bvh.root_ref;
     D.n_tris = d->n_triangles;
     D.n_nodes = s->bvh_nodes;
-    D.pad_nodes = 0;
+    D.tri_geo = s->tri_geo;
     D.positions = s->positions.as<float>();
     D.normals = d->normals ? s->normals.as<float>() : nullptr;
     D.uvs = d->uvs ? s->uvs.as<float>() : nullptr;
@@ -798,6 +802,11 @@ extern "C" int32_t hk_scene_create(hk_ctx* c, const hk_scene_desc* d, hk_scene**
     std::vector<DMedium> dmed;
     if (int e = upload_media(s, d, c->r2s_host, dmed)) return e;
     fill_dscene(s, d, bu, surf.all_opaque, has_escape, classify_media(dmed, d->n_media));
+    if (s->d.tri_geo) {   // the geometry rows of every triangle, by the function surface_at would call (finished before the scene is handed out)
+        hk::launch_tri_geo(c->stream, s->positions.as<float>(), d->n_triangles, s->d.tri_geo, s->tri_shade.p ? s->tri_shade.as<float>() : nullptr);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
     note_edit_tables(s, d, bvh, bu.have_qnodes);
     *out = guard.release();
     return HK_OK;

@@ -155,7 +155,7 @@ extern "C" int32_t hk_scene_set_transform(hk_scene* s, int32_t first_tri, int32_
     if (int e = ensure_base(s)) return e;
     hk::launch_xform_tris(c->stream, X, first_tri, n_tris, s->base_pos.as<float>(), D.normals ? s->base_nrm.as<float>() : nullptr, D.tangents ? s->base_tan.as<float>() : nullptr,
                           s->slot_of_prim.as<int>(), s->positions.as<float>(), D.normals ? s->normals.as<float>() : nullptr, D.tangents ? s->tangents.as<float>() : nullptr,
-                          D.tri_shade ? s->tri_shade.as<float>() : nullptr, s->leaf_tris.as<float4>());
+                          D.tri_shade ? s->tri_shade.as<float>() : nullptr, tri_geo_rows(s->positions.as<float>(), D.tri_geo), s->leaf_tris.as<float4>());
     HIP_TRY(hipGetLastError());
     {   // the transform of every triangle interval (the quantised grid's bookkeeping)
         const int a = first_tri, e = first_tri + n_tris;
@@ -727,6 +727,7 @@ extern "C" int32_t hk_scene_set_vertices(hk_scene* s, int32_t first_tri, int32_t
     A.tan = D.tangents ? s->tangents.as<float>() : nullptr;
     A.uvs = D.uvs ? s->uvs.as<float>() : nullptr;
     A.shade = D.tri_shade ? s->tri_shade.as<float>() : nullptr;
+    A.geo = tri_geo_rows(s->positions.as<float>(), D.tri_geo);
     A.slot_of_prim = s->slot_of_prim.as<int>();
     A.leaf = s->leaf_tris.as<float4>();
     hk::launch_set_tris(c->stream, A);

@@ -565,13 +565,15 @@ __device__ __forceinline__ void lds_fetch16(const float4* src, float4* lds_wave_
 // mat_id's own bit.  The fetch-ahead needs no queue entry: the next chunk's slots are this chunk's + 64, requested near the top of a chunk,
 // behind the emission block (all lanes, escaped ones too: their successors may hold hits), the mat_id word with them in stage.entry[0 .. 255].  Shadow and continuing
 // records are appended in walk order, so every generation of a segment stays in ascending path-slot order down the bounces.
-template <int KIND, bool SIMPLE, bool FT, bool PRE, bool LEAN = false, bool SLOTS = false>
+// GEO (LEAN): surface_at reads the hit triangle's geometric normal and area from the scene's table (DScene::tri_geo) instead of the positions.
+template <int KIND, bool SIMPLE, bool FT, bool PRE, bool LEAN = false, bool SLOTS = false, bool GEO = false>
 __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& sc, const DTables& T, const DFrame& fr, const DSobol& sob, int depth, int first_kind, DStats* stats, const SegTickets& src,
                                            uint32_t* __restrict__ elist,   // elist: this wave's 128 LDS words (slots of flagged — emissive-hit — vertices waiting for the dense K8 pass)
                                            float* stash = nullptr,         // LEAN: the block's HK_SHADE_STASH * 256 LDS words
                                            ShadeStage stage = ShadeStage{}) {   // LEAN: the block's staging area of the fetch-ahead (null pointers: none)
     static_assert(!LEAN || (KIND == HK_MAT_MATTE && HK_LAMBDA_BY_SLOT), "the lean body is Matte's");
     static_assert(!SLOTS || LEAN, "the slot walk is the lean body's");
+    static_assert(!GEO || LEAN, "the geometry table is read by the lean body");
     const int lane = lane_id();
     unsigned n_vertices = 0, n_lnodes = 0;
     unsigned nv_wave = 0;   // LEAN: the vertices of the whole wave
@@ -652,9 +654,9 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
         uint32_t meta_staged = 0;
         uint32_t slot;
         bool em_slot = false;
+        uint32_t mat_w = HK_MAT_ESCAPED;   // SLOTS: the path's mat_id word (the vertex takes its material index from it)
         if constexpr (SLOTS) {
             slot = (uint32_t)seg + (uint32_t)i;   // generation index of the path: the segment's entries in order
-            uint32_t mat_w = HK_MAT_ESCAPED;
             if (staged) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the staged records have landed
                 const uint32_t w = stage.entry[(int)threadIdx.x];
@@ -721,6 +723,9 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
             if constexpr (!LEAN) ++n_vertices;
             float4 D;
             uint32_t meta_w = 0;   // LEAN: the record's 32-bit meta word (path slot, specular and any-non-specular bits)
+            // the vertex's material record: mat_id read ONCE for this half (SLOTS: not at all — the chunk holds the word); the second half
+            // reads it again rather than keep a register across the light's choice and sample
+            const int mat_idx = (SLOTS ? (int)mat_w : st.mat_id[slot]) & ~HK_MAT_EMISSIVE_BIT;
             if (SLOTS && staged)
                 D = D_staged, meta_w = meta_staged;   // (and H: read at the top of the chunk)
             else if (LEAN && staged) {
@@ -736,7 +741,7 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
             v3 ro = mk3(O.x, O.y, O.z), rd = mk3(D.x, D.y, D.z);
             float t_hit = H.x;
             int prim = __float_as_int(H.y);
-            sf = surface_at(sc, prim, H.z, H.w, ro, rd, t_hit);
+            sf = surface_at<GEO>(sc, prim, H.z, H.w, ro, rd, t_hit);
             wo = -rd;
             meta = tri_meta(sc, prim);
             if constexpr (LEAN) {
@@ -765,7 +770,7 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
             split_slot(fr, pslot, pix, k);
             sctx = sobol_ctx_slot(sob, T.sobol, fr.x0, fr.y0, fr.tiles_x, pix, k, fr.first_sample + k * fr.sample_stride);
 
-            if (KIND == HK_MAT_MATTE) kd_matte = matte_kd<SIMPLE>(sc, T, sc.materials[st.mat_id[slot] & ~HK_MAT_EMISSIVE_BIT], TexCtx(sf.uv, meta.prim_index, H.z, H.w), lambda);
+            if (KIND == HK_MAT_MATTE) kd_matte = matte_kd<SIMPLE>(sc, T, sc.materials[mat_idx], TexCtx(sf.uv, meta.prim_index, H.z, H.w), lambda);
 #ifdef HK_ABLATE
             // cost attribution by duplication (tools/ablate.md): stage HK_ABLATE runs a second time on laundered inputs, its result is
             // kept alive but unused; the k_shade time delta against the plain build is that stage's cost.  Never defined in the product.
@@ -797,13 +802,13 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
                 if (HK_ABLATE == 4) {   // matte_kd (spectral reflectance at four wavelengths)
                     S4 l2 = lambda;
                     asm volatile("" : "+v"(l2.x), "+v"(l2.y), "+v"(l2.z), "+v"(l2.w));
-                    S4 k2 = matte_kd(sc, T, sc.materials[st.mat_id[slot] & ~HK_MAT_EMISSIVE_BIT], TexCtx(sf.uv, meta.prim_index, H.z, H.w), l2);
+                    S4 k2 = matte_kd(sc, T, sc.materials[mat_idx], TexCtx(sf.uv, meta.prim_index, H.z, H.w), l2);
                     sink = k2.x + k2.y + k2.z + k2.w;
                 }
                 if (HK_ABLATE == 5) {   // surface_at
                     float b2 = H.z;
                     asm volatile("" : "+v"(b2));
-                    Surface s2 = surface_at(sc, prim, b2, H.w, ro, rd, t_hit);
+                    Surface s2 = surface_at<GEO>(sc, prim, b2, H.w, ro, rd, t_hit);
                     sink = s2.pi.x + s2.n.y + s2.ns.z + s2.uv.x + s2.area;
                 }
                 if (HK_ABLATE == 6) {   // eval_matte_kd + sample_matte_kd on laundered directions
@@ -811,8 +816,15 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
                     asm volatile("" : "+v"(w2.x), "+v"(w2.y), "+v"(w2.z));
                     float p2;
                     S4 f2 = eval_matte_kd(kd_matte, w2, sf.n, sf.ns, p2);
-                    BSDFSample s2 = sample_matte_kd(sc, sc.materials[st.mat_id[slot] & ~HK_MAT_EMISSIVE_BIT], kd_matte, w2, sf.ns, TexCtx(sf.uv, meta.prim_index, H.z, H.w), mk2(H.z, H.w));
+                    BSDFSample s2 = sample_matte_kd(sc, sc.materials[mat_idx], kd_matte, w2, sf.ns, TexCtx(sf.uv, meta.prim_index, H.z, H.w), mk2(H.z, H.w));
                     sink = f2.x + f2.w + p2 + s2.pdf + s2.wi.x + s2.f.y;
+                }
+                if (HK_ABLATE == 7) {   // the mat_id -> material record fetches of a matte vertex (Kd's coefficients, sigma) on a laundered slot
+                    uint32_t s2 = slot;
+                    asm volatile("" : "+v"(s2));
+                    const DMaterial& m2 = sc.materials[st.mat_id[s2] & ~HK_MAT_EMISSIVE_BIT];
+                    const float4 c2 = m2.rgb[0].coef;
+                    sink = c2.x + c2.y + c2.z + c2.w + eval_f32<SIMPLE>(sc, m2, 0, TexCtx(sf.uv, meta.prim_index, H.z, H.w));
                 }
                 asm volatile("" : : "v"(sink));
             }
@@ -836,7 +848,7 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
             }
             // ---- K9: next-event estimation through the light BVH ----
             if (sc.n_lights > 0) {
-                const DMaterial& mat = sc.materials[st.mat_id[slot] & ~HK_MAT_EMISSIVE_BIT];
+                const DMaterial& mat = sc.materials[mat_idx];
                 float light_pmf;
                 int light_idx;
                 if constexpr (PRE) {
@@ -1017,7 +1029,7 @@ __device__ __forceinline__ void shade_body(const DPathState& st, const DScene& s
     wave_add(&stats->vertices, n_vertices);
     wave_add(&stats->light_nodes, n_lnodes);
 }
-template <int KIND, bool SIMPLE = false, bool FT = false, bool PRE = false, bool LEAN = false, bool SLOTS = false>
+template <int KIND, bool SIMPLE = false, bool FT = false, bool PRE = false, bool LEAN = false, bool SLOTS = false, bool GEO = false>
 __global__ void __attribute__((amdgpu_flat_work_group_size(256, 256), amdgpu_waves_per_eu(LEAN ? (FT ? HK_SHADE_WAVES_LEAN : HK_SHADE_WAVES_LEAN_HASH) : ShadeWaves<KIND>::value))) k_shade(DPathState st, DScene sc, DTables T, DFrame fr, DSobol sob, int depth, int first_kind, DStats* stats) {
     __shared__ uint32_t emit_list[4 * 128];
     SegTickets src = seg_open(st, ticket_ptr(st, depth, TK_SHADE0 + KIND), st.dynamic_segments != 0, depth, Q_MAT0 + KIND);
@@ -1031,7 +1043,7 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(256, 256), amdgpu_wav
         __shared__ uint32_t stage_meta[256];
         ShadeStage stage{};
         if (st.shade_prefetch) stage.entry = stage_entry, stage.hit = stage_hit, stage.ray_d = stage_ray_d, stage.meta = stage_meta;
-        shade_body<KIND, SIMPLE, FT, PRE, true, SLOTS>(st, sc, T, fr, sob, depth, first_kind, stats, src, emit_list + (threadIdx.x >> 6) * 128, stash, stage);
+        shade_body<KIND, SIMPLE, FT, PRE, true, SLOTS, GEO>(st, sc, T, fr, sob, depth, first_kind, stats, src, emit_list + (threadIdx.x >> 6) * 128, stash, stage);
     } else
         shade_body<KIND, SIMPLE, FT, PRE>(st, sc, T, fr, sob, depth, first_kind, stats, src, emit_list + (threadIdx.x >> 6) * 128);
 }

@@ -15,7 +15,7 @@
 // For: all-opaque scenes without media, escape lights or light preselection whose only material kind is Matte under simple lights
 // (launch_small_pass says which; everything else keeps the launches).
 // ---------------------------------------------------------------------------------------------------
-template <typename ACC>
+template <typename ACC, int G = 1>   // (G = 1: the wave's 256 staging floats, all a stack has to spare)
 __device__ __forceinline__ void film_tile(const DPathState& st, const DFrame& fr, const DTables& T, ACC* __restrict__ accum, float* __restrict__ mine, int tile);
 __device__ __forceinline__ void stage_fence() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");

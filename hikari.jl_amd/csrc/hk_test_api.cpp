@@ -219,3 +219,23 @@ extern "C" int32_t hk_test_queue_counts(hk_integrator* I, int32_t depth, int32_t
     }
     return HK_OK;
 }
+
+extern "C" int32_t hk_test_tri_geo(hk_scene* s, int32_t recompute, int32_t* n_tris, int32_t* has_table, float* out4) {
+    if (!s || !n_tris) return fail(HK_ERR_INVALID, "hk_test_tri_geo: null argument");
+    const int T = s->d.n_tris;
+    *n_tris = T;
+    if (has_table) *has_table = s->d.tri_geo != 0 ? 1 : 0;
+    if (!out4 || T == 0) return HK_OK;
+    if (!recompute && s->d.tri_geo == 0) return fail(HK_ERR_INVALID, "hk_test_tri_geo: the scene has no geometry table");
+    hk_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    KnobScope knobs(&c->knobs);
+    if (int e = join_lanes(c)) return e;
+    Tmp t;
+    float* o = t.up<float>(nullptr, 4 * (size_t)T);
+    hk::launch_test_tri_geo(c->stream, s->d, recompute ? 1 : 0, reinterpret_cast<float4*>(o));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(out4, o, 4 * (size_t)T * sizeof(float), hipMemcpyDeviceToHost));
+    return HK_OK;
+}

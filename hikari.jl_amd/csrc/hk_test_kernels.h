@@ -20,6 +20,17 @@ __global__ void __launch_bounds__(HK_TRACE_BLOCK) k_test_trace(DScene sc, int n,
         out_uv[2 * i + 1] = h.prim >= 0 ? h.v : 0.0f;
     }
 }
+// hk_test_tri_geo: the geometry table's rows as surface_at reads them, or the shared function on the positions the device holds
+__global__ void __launch_bounds__(256) k_test_tri_geo(DScene sc, int recompute, float4* __restrict__ out) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < sc.n_tris; i += gridDim.x * blockDim.x) {
+        if (recompute) {
+            v3 a, b, c;
+            tri_vertices(sc, i, a, b, c);
+            out[i] = tri_geo_of(a, b, c);
+        } else
+            out[i] = tri_geo_row(sc, i);
+    }
+}
 __global__ void k_test_sobol(DTables T, DSobol sob, int n, const int* px, const int* py, const int* sidx, const int* dim, float* o1, float* o2) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         SobolCtx c = sobol_ctx(sob, T.sobol, px[i], py[i], sidx[i]);
@@ -253,6 +264,9 @@ void launch_test_trace_lean(hipStream_t s, int n_cu, const DScene& sc, int anyhi
         else if (sc.qnodes != nullptr) launch(k_test_trace_lean<a, HK_LDS_STACK, true>);   // the kernels' own choice for a deep tree: its quantised nodes
         else launch(k_test_trace_lean<a, HK_LDS_STACK>);
     });
+}
+void launch_test_tri_geo(hipStream_t s, const DScene& sc, int recompute, float4* out) {
+    if (sc.n_tris > 0) hipLaunchKernelGGL(k_test_tri_geo, dim3(grid_for(sc.n_tris, 256, 8192)), dim3(256), 0, s, sc, recompute, out);
 }
 void launch_test_trace(hipStream_t s, const DScene& sc, int n, const float* o, const float* d, const float* tmax, float* t, int* prim, float* uv) {
     hipLaunchKernelGGL(k_test_trace, dim3(grid_for(n, HK_TRACE_BLOCK, 1280)), dim3(HK_TRACE_BLOCK), 0, s, sc, n, o, d, tmax, t, prim, uv);

@@ -267,6 +267,7 @@ struct DSetTris {
     const float *in_pos, *in_nrm, *in_tan, *in_uv;
     float *base_pos, *base_nrm, *base_tan;
     float *pos, *nrm, *tan, *uvs, *shade;
+    float4* geo;               // the geometry table's rows (DScene::tri_geo; a scene with packed records keeps them in `shade`)
     const int* slot_of_prim;
     float4* leaf;
 };
@@ -319,7 +320,12 @@ struct DScene {
     int root_ref;
     int n_tris;
     int n_nodes;                // inner nodes, breadth-first: the first HK_NODE_CACHE of them are what the lean traversal kernels keep in LDS
-    int pad_nodes;
+    // PER-TRIANGLE GEOMETRY (tri_geo_of, hk_device.h): the geometric normal and the area of every triangle, (n.x, n.y, n.z, area) in
+    // original triangle order, written wherever positions are written.  0: surface_at computes them from the positions at every vertex
+    // (HK_TRI_GEO=0, per launch: launch_impl's with_tri_geo).  Else a scene with packed records keeps the row in words 28 .. 31 of
+    // the record, any other scene in a float4 array behind the positions, in the same allocation: tri_geo is its offset in floats
+    // (this word was padding: the struct, and with it the argument layout of every kernel, stays as it was).
+    int tri_geo;
     const float* positions;     // [T][9]
     const float* normals;       // [T][9] or null
     const float* uvs;           // [T][6] or null
@@ -357,6 +363,9 @@ struct DScene {
     int has_mix;                // a material record is a MixMaterial (hk_scene_create, hk_scene_update_materials): 0 selects the closest-hit kernel without the resolve
     int single_kind;            // the kind of EVERY material record when they share one and none is a Mix (a launch constant of that kernel's flush), else -1
 };
+// the rows of the geometry table behind the positions (DScene::tri_geo > 1; hk::tri_geo_word, hk_edit_host.h), null for a scene that
+// keeps them in its packed records (1) or has no table (0)
+__host__ __device__ inline float4* tri_geo_rows(float* positions, int tri_geo) { return tri_geo > 1 ? reinterpret_cast<float4*>(positions + tri_geo) : nullptr; }
 
 struct DTables {
     const uint32_t* sobol;      // dims 0 and 1 (2 x 52)

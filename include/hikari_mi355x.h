@@ -747,6 +747,13 @@ int32_t hk_test_medium_bricks(hk_scene* scene, int32_t idx, int32_t* dims, float
    max_depth 1: depth 0).  kind -1: the rays of the generation at `depth` (hits and escaped together), kind -2: those of them that escaped
    (both without `flagged`).  Staged passes only (a pass rendered in one fused launch leaves no counts); waits for the context's stream. */
 int32_t hk_test_queue_counts(hk_integrator* integrator, int32_t depth, int32_t kind, int32_t* n_segments, int32_t* counts, int32_t* flagged);
+/* The per-triangle geometry table of the scene, (n.x, n.y, n.z, area) per triangle in original triangle order — what the shading
+   kernels read in place of the three vertex positions (context option HK_TRI_GEO=0: they compute it from the positions at every
+   vertex, the same bits).  *n_tris = the scene's triangle count; out4 (NULL: only the count) = 4 floats per triangle: recompute 0 the
+   rows as the device holds them (from the packed shading records where the scene has them), recompute 1 the rows a kernel computes
+   now from the world positions the device holds, by the function that fills the table.  *has_table (NULL: not wanted) = 0 for a scene
+   without one (no triangles): recompute 0 is then an error.  Waits for the context's stream. */
+int32_t hk_test_tri_geo(hk_scene* scene, int32_t recompute, int32_t* n_tris, int32_t* has_table, float* out4);
 
 #ifdef __cplusplus
 }
