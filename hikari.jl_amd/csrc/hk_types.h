@@ -272,7 +272,7 @@ struct DSetTris {
     float4* leaf;
 };
 
-// hk_scene_rebuild_bvh: the device builder's state (k_build_*, hk_kernels.hip).  A SEGMENT is a range of the index array that becomes
+// hk_scene_rebuild_bvh: the device builder's state (k_build_*, hk_build_kernels.h).  A SEGMENT is a range of the index array that becomes
 // an inner node: level L's segments, in breadth-first order, are nodes level_start[L] + 0, 1, ...; `large` >= 0 names the segment's
 // slot in the global bin storage (it is binned by many blocks), < 0: one block bins it in LDS.
 #define HK_BUILD_MAX_LEVELS 31   // = HK_BVH_MAX_LEVELS (hk_bvh_decide.h)
