@@ -20,6 +20,6 @@ from .media import GridMedium, HomogeneousMedium, NanoVDBMedium, RGBGridMedium
 from .media_presets import Coffee, Fog, Juice, Milk, Smoke, SubsurfaceMedium, Wine, get_medium_preset
 from .postprocess import FilmSensor, compute_white_balance_matrix
 from .scene import Scene
-from .sunsky import sunsky_to_envlight
+from .sunsky import sky_params, sky_texels, sunsky_to_envlight
 from .volpath import (BoxFilter, Comm, Context, GaussianFilter, LanczosSincFilter, MitchellFilter, TriangleFilter, VolPath,
                       integrator_params, scene_handle)

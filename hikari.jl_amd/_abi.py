@@ -85,6 +85,11 @@ class hk_dense_field(C.Structure):
     _fields_ = [("data", PF), ("res", c_i * 3), ("layout", c_i), ("on_device", c_i)]
 
 
+class hk_sky_params(C.Structure):
+    _fields_ = [("sun_dir", c_f * 3), ("ground_enabled", c_i), ("ground_rgb", c_f * 3), ("reserved", c_i),
+                ("config", (C.c_double * 9) * 11), ("radiance", C.c_double * 11), ("xyz_weight", (C.c_double * 13) * 3)]
+
+
 class hk_scene_desc(C.Structure):
     _fields_ = [("n_triangles", c_i), ("n_materials", c_i), ("n_textures", c_i), ("n_media_interfaces", c_i),
                 ("n_lights", c_i), ("n_envmaps", c_i), ("n_media", c_i), ("n_spectra", c_i), ("positions", PF),
@@ -151,9 +156,10 @@ EXPORTED_SYMBOLS = [
     "hk_film_update_aux", "hk_film_read_aux", "hk_film_present", "hk_film_present_async",
     "hk_scene_update_medium", "hk_scene_medium_copy", "hk_test_medium_bricks", "hk_scene_set_vertices", "hk_scene_bvh_cost", "hk_scene_bvh_copy",
     "hk_scene_bvh_leaves", "hk_scene_rebuild_bvh", "hk_test_queue_counts", "hk_test_tri_geo", "hk_scene_update_medium_dense", "hk_scene_medium_tree_copy",
+    "hk_scene_update_envmap_sky", "hk_scene_envmap_copy",
 ]
 
-# prototypes (argtypes, restype) of the geometry edit, the tree introspection and the dense-field medium update, in the header's order;
+# prototypes (argtypes, restype) of the geometry edit, the tree introspection, the dense-field medium update and the sky bake, in the header's order;
 # _lib.py installs them
 _VP, _I32, _PI32, _PD = C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double)
 PROTOTYPES = {
@@ -164,4 +170,6 @@ PROTOTYPES = {
     "hk_scene_rebuild_bvh": ([_VP], _I32),
     "hk_scene_update_medium_dense": ([_VP, _I32, C.POINTER(hk_medium), C.POINTER(hk_dense_field)], _I32),
     "hk_scene_medium_tree_copy": ([_VP, _I32, C.POINTER(hk_medium), C.POINTER(C.c_int64), C.POINTER(C.c_uint8), _PI32, _PI32, C.POINTER(C.c_uint32)], _I32),
+    "hk_scene_update_envmap_sky": ([_VP, _I32, C.POINTER(hk_sky_params)], _I32),
+    "hk_scene_envmap_copy": ([_VP, _I32, _PI32, _PI32, PF, PF, PF, PF, PF, PF], _I32),
 }

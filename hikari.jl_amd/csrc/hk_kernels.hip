@@ -1,7 +1,7 @@
 // hk_kernels.hip — the device code of the library for gfx950 (wave64): ONE translation unit (DESIGN.md §4 describes the pass).
 // The headers are slices of it, not modules: each uses what stands above it, and the order of the kernels in the code object is the
 // order of this list.  Keep the order; a new kernel goes into the header of its stage.  This file holds no code of its own:
-//     hk_device.h, hk_edit_host.h, hk_bvh_decide.h    not slices: the device library, and the arithmetic shared with the host
+//     hk_device.h, hk_edit_host.h, hk_bvh_decide.h, hk_sky.h    not slices: the device library, and the arithmetic shared with the host
 //     hk_wave_queues.h    lane_id, WaveQ, segment tickets and loops, streaming loads / stores, record loaders, HK_DBG*
 //     hk_camera_stage.h    k_sobol_table, k_segment_lists, k_sobol_lo_table, k_camera                                      [K1]
 //     hk_traverse.h        LDS cache fills, k_trace, the per-lane ray state machine, k_trace_lean                          [K3]
@@ -16,6 +16,7 @@
 //     hk_build_kernels.h   k_build_*: the device BVH build
 //     hk_table_kernels.h   k_envmap_*, k_majorant_*, k_nvdb_bricks
 //     hk_nvdb_build.h      a NanoVDB tree from a dense field
+//     hk_sky_kernels.h     k_sky_texels: a Hosek-Wilkie sky baked into an environment map
 //     hk_launch_impl.h     the launch layer (hk_launch.h), which names every kernel
 //     hk_test_kernels.h    the parity tests' entry points
 #include <hip/hip_runtime.h>
@@ -27,6 +28,7 @@
 #include "hk_device.h"
 #include "hk_edit_host.h"
 #include "hk_bvh_decide.h"
+#include "hk_sky.h"
 
 using namespace hkd;
 
@@ -46,5 +48,6 @@ namespace {
 #include "hk_build_kernels.h"
 #include "hk_table_kernels.h"
 #include "hk_nvdb_build.h"
+#include "hk_sky_kernels.h"
 #include "hk_launch_impl.h"
 #include "hk_test_kernels.h"

@@ -62,6 +62,8 @@ void launch_bvh_cost(hipStream_t s, const DNode* nodes, int n, double* partial);
 void launch_bvh_build(hipStream_t s, const DBuild& B);
 void launch_bvh_build_leaves(hipStream_t s, const DBuildLeaves& A);
 void launch_envmap_tables(hipStream_t s, const DEnvMap& e, DEnvMap* record);
+// hk_scene_update_envmap_sky: the res x res texels of a Hosek-Wilkie sky into `data` (launch_envmap_tables follows)
+void launch_sky_texels(hipStream_t s, const hk_sky_params& sky, int res, float4* data);
 // hk_scene_update_medium: majorant grid + zero-cell mask of a Grid / RGB grid / NanoVDB medium, and the NanoVDB halo bricks, from the data `m` points to
 void launch_majorant_grid(hipStream_t s, const DMedium& m);
 void launch_majorant_nanovdb(hipStream_t s, const DMedium& m, const DIndexBox& index_bbox);

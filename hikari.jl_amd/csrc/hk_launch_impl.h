@@ -484,6 +484,9 @@ void launch_envmap_tables(hipStream_t s, const DEnvMap& e, DEnvMap* record) {
                        const_cast<float*>(e.cond_func_int), const_cast<float*>(e.marg_func));
     hipLaunchKernelGGL(k_envmap_marginal, dim3(1), dim3(64), 0, s, e.nv, e.marg_func, const_cast<float*>(e.marg_cdf), record);
 }
+void launch_sky_texels(hipStream_t s, const hk_sky_params& sky, int res, float4* data) {
+    hipLaunchKernelGGL(k_sky_texels, dim3((unsigned)(((long long)res * res + 255) / 256)), dim3(256), 0, s, sky, res, data);
+}
 
 // The tables hk_scene_update_medium derives from the volume data of `m` (a host copy of the record the device will hold: sizes and the
 // pointers to data already enqueued on `s`): the majorant grid into m.majorant, then its zero-cell mask into m.maj_zero.  A cell goes to

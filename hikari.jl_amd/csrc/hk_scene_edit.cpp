@@ -1,6 +1,7 @@
 // hk_scene_edit.cpp — in-place scene edits: hk_scene_set_transform (device transform + BVH refit), hk_scene_set_vertices (new base
 // geometry of a triangle range in one device pass + BVH refit), hk_scene_update_materials, hk_scene_update_lights (records + host
-// rebuild of the light BVH), hk_scene_update_envmap (rotation, texels + device table build) and hk_scene_update_medium (record, volume
+// rebuild of the light BVH), hk_scene_update_envmap (rotation, texels + device table build), hk_scene_update_envmap_sky (the texels of
+// a Hosek-Wilkie sky evaluated on the device; hk_scene_envmap_copy reads a map back) and hk_scene_update_medium (record, volume
 // data + device build of majorant grid, zero-cell mask and NanoVDB bricks), hk_scene_update_medium_dense (the NanoVDB tree of a dense
 // field and its block table built on the device as well) and hk_scene_rebuild_bvh (a new BVH topology built on the
 // device); hk_scene_bvh_cost / hk_scene_bvh_copy / hk_scene_bvh_leaves read the tree back, hk_scene_medium_tree_copy a NanoVDB tree.
@@ -25,7 +26,8 @@
 // tree that grows past the threshold is preselected from the next call on, as a fresh scene's would be (the path state carries sel_light
 // whenever the scene has no media, whatever the count); k_light_select_pool's LDS copy of the top of the tree is filled per launch from
 // num_bvh_lights.  The infinite list is a function of the kinds alone and stays as uploaded.
-// hk_scene_update_envmap changes texels, tables and rotation of a map of unchanged size: nothing on the host is derived from those.
+// hk_scene_update_envmap changes texels, tables and rotation of a map of unchanged size: nothing on the host is derived from those
+// (hk_scene_update_envmap_sky: texels and tables only).
 // hk_scene_update_medium changes one medium's record and the data behind it; what it leaves valid is said at the entry point below.
 namespace {
 // the transform of the header's arithmetic: m as given, its normal matrix in double, identity => copy
@@ -326,6 +328,62 @@ extern "C" int32_t hk_scene_update_envmap(hk_scene* s, int32_t idx, const float*
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(st->ev, c->stream));
+    return HK_OK;
+}
+
+// The texels of map `idx` from a sky record, on the device (k_sky_texels), then the tables from them as above.  The record is a kernel
+// argument, so nothing is staged and nothing of the caller's is read after the call returns.
+extern "C" int32_t hk_scene_update_envmap_sky(hk_scene* s, int32_t idx, const hk_sky_params* sky) {
+    if (!sky) return fail(HK_ERR_INVALID, "hk_scene_update_envmap_sky: null params");
+    if (!s) return fail(HK_ERR_INVALID, "hk_scene_update_envmap_sky: null scene");
+    if (idx < 0 || idx >= (int)s->h_envmaps.size()) return fail(HK_ERR_INVALID, "hk_scene_update_envmap_sky: map index out of range");
+    const DEnvMap& e = s->h_envmaps[idx];
+    if (e.width != e.height) return fail(HK_ERR_INVALID, "hk_scene_update_envmap_sky: the map is not square");
+    if (e.nu != e.width || e.nv != e.height) return fail(HK_ERR_INVALID, "hk_scene_update_envmap_sky: the map's tables are not of its texels' resolution (nu != width or nv != height)");
+    if (sky->reserved != 0) return fail(HK_ERR_INVALID, "hk_scene_update_envmap_sky: reserved is not 0");
+    bool finite = true;
+    for (int j = 0; j < 3; ++j) finite = finite && std::isfinite(sky->sun_dir[j]) && std::isfinite(sky->ground_rgb[j]);
+    const double* d = &sky->config[0][0];
+    for (int j = 0; j < 11 * 9; ++j) finite = finite && std::isfinite(d[j]);
+    for (int j = 0; j < 11; ++j) finite = finite && std::isfinite(sky->radiance[j]);
+    d = &sky->xyz_weight[0][0];
+    for (int j = 0; j < 3 * 13; ++j) finite = finite && std::isfinite(d[j]);
+    if (!finite) return fail(HK_ERR_INVALID, "hk_scene_update_envmap_sky: non-finite entry in the record");
+    const double len2 = ((double)sky->sun_dir[0] * sky->sun_dir[0] + (double)sky->sun_dir[1] * sky->sun_dir[1]) + (double)sky->sun_dir[2] * sky->sun_dir[2];
+    if (!(len2 >= 1.0 - 1e-3 && len2 <= 1.0 + 1e-3)) return fail(HK_ERR_INVALID, "hk_scene_update_envmap_sky: sun_dir is not a unit vector (squared length outside 1 +- 1e-3)");
+    hk_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    KnobScope knobs(&c->knobs);
+    if (int err = join_lanes(c)) return err;   // noted calls render the old sky; the lanes finish before the stream rewrites it
+    hk::launch_sky_texels(c->stream, *sky, e.width, const_cast<float4*>(e.data));
+    hk::launch_envmap_tables(c->stream, e, s->envmaps.as<DEnvMap>() + idx);
+    HIP_TRY(hipGetLastError());
+    return HK_OK;
+}
+
+extern "C" int32_t hk_scene_envmap_copy(hk_scene* s, int32_t idx, int32_t* width, int32_t* height, float* texels, float* conditional_func, float* conditional_cdf, float* marginal_func,
+                                        float* marginal_cdf, float* marginal_func_int) {
+    if (!s) return fail(HK_ERR_INVALID, "hk_scene_envmap_copy: null scene");
+    if (idx < 0 || idx >= (int)s->h_envmaps.size()) return fail(HK_ERR_INVALID, "hk_scene_envmap_copy: map index out of range");
+    const DEnvMap& e = s->h_envmaps[idx];
+    if ((conditional_func || conditional_cdf || marginal_func || marginal_cdf) && (e.nu != e.width || e.nv != e.height))   // a caller sizes its buffers from width and height
+        return fail(HK_ERR_INVALID, "hk_scene_envmap_copy: the map's tables are not of its texels' resolution (nu != width or nv != height): only sizes, texels and marginal_func_int can be read");
+    if (width) *width = e.width;
+    if (height) *height = e.height;
+    if (!texels && !conditional_func && !conditional_cdf && !marginal_func && !marginal_cdf && !marginal_func_int) return HK_OK;
+    hk_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    KnobScope knobs(&c->knobs);
+    if (int err = join_lanes(c)) return err;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const size_t nu = (size_t)e.nu, nv = (size_t)e.nv;
+    if (texels) HIP_TRY(hipMemcpy(texels, e.data, (size_t)e.width * e.height * 16, hipMemcpyDeviceToHost));
+    if (conditional_func) HIP_TRY(hipMemcpy(conditional_func, e.cond_func, nu * nv * 4, hipMemcpyDeviceToHost));
+    if (conditional_cdf) HIP_TRY(hipMemcpy(conditional_cdf, e.cond_cdf, (nu + 1) * nv * 4, hipMemcpyDeviceToHost));
+    if (marginal_func) HIP_TRY(hipMemcpy(marginal_func, e.marg_func, nv * 4, hipMemcpyDeviceToHost));
+    if (marginal_cdf) HIP_TRY(hipMemcpy(marginal_cdf, e.marg_cdf, (nv + 1) * 4, hipMemcpyDeviceToHost));
+    if (marginal_func_int)   // the device record's own copy: only the device knows it after a table build
+        HIP_TRY(hipMemcpy(marginal_func_int, reinterpret_cast<const char*>(s->envmaps.as<DEnvMap>() + idx) + offsetof(DEnvMap, marg_func_int), 4, hipMemcpyDeviceToHost));
     return HK_OK;
 }
 

@@ -71,16 +71,54 @@ class EnvironmentMap:
     data[v, u]; the sampling distribution is the texel luminance to_Y (no sin(theta): equal-area)."""
 
     def __init__(self, data, rotation=None):
+        self._sky = None            # set_sky: the texels are a sky the host has not baked yet
+        self.rotation = np.eye(3, dtype=f32) if rotation is None else np.asarray(rotation, dtype=f32).reshape(3, 3)
+        self._data, self._distribution, self._jl = self._texels_and_tables(data)
+        self.height, self.width = self._data.shape[:2]
+
+    @staticmethod
+    def _texels_and_tables(data):
         d = np.asarray(data, dtype=f32)
         assert d.ndim == 3 and d.shape[2] in (3, 4)
         if d.shape[2] == 3:
             d = np.concatenate([d, np.ones(d.shape[:2] + (1,), f32)], axis=2)
-        self.data = np.ascontiguousarray(d)
-        self.height, self.width = d.shape[:2]
-        self.rotation = np.eye(3, dtype=f32) if rotation is None else np.asarray(rotation, dtype=f32).reshape(3, 3)
+        d = np.ascontiguousarray(d)
         lum = f32(0.212671) * d[..., 0] + f32(0.715160) * d[..., 1] + f32(0.072169) * d[..., 2]   # to_Y (spectrum.jl:74-76)
-        self.distribution = Distribution2D(lum.astype(f32))
-        self._jl = np.ascontiguousarray(np.transpose(self.data, (1, 0, 2)))   # [x][y][4] == Julia [h, w] column-major
+        return d, Distribution2D(lum.astype(f32)), np.ascontiguousarray(np.transpose(d, (1, 0, 2)))   # [x][y][4] == Julia [h, w] column-major
+
+    # data and distribution are what the host holds of the map.  After set_sky they are a bake the host still owes: reading either (or
+    # record()) runs it, once.
+    @property
+    def data(self):
+        self.bake()
+        return self._data
+
+    @property
+    def distribution(self):
+        self.bake()
+        return self._distribution
+
+    def set_sky(self, **sky):
+        """The texels become the sky sunsky.sky_texels(**sky, resolution=height) bakes — LATER: nothing is computed here (a device scene
+        bakes its own texels, hk_scene_update_envmap_sky).  The host bake runs when data, distribution or record() is asked for."""
+        if self.height != self.width:
+            raise ValueError("set_sky: the map is %dx%d (a sky is baked into a square map)" % (self.width, self.height))
+        self._sky = dict(sky)
+
+    def bake(self):
+        """Run the host bake set_sky left pending (no-op otherwise), into the arrays a record() already handed out."""
+        if self._sky is None:
+            return
+        sky, self._sky = self._sky, None
+        from . import sunsky
+        self._assign(*self._texels_and_tables(sunsky.sky_texels(resolution=self.height, **sky)))
+
+    def _assign(self, data, distribution, jl):
+        self._data[...] = data
+        self._jl[...] = jl
+        for name in self._TABLES:
+            getattr(self._distribution, name)[...] = getattr(distribution, name)
+        self._distribution.marginal_func_int = distribution.marginal_func_int
 
     _TABLES = ("conditional_func", "conditional_cdf", "conditional_func_int", "marginal_func", "marginal_cdf")
 
@@ -99,17 +137,14 @@ class EnvironmentMap:
             new = EnvironmentMap(data)
             if (new.height, new.width) != (self.height, self.width):
                 raise ValueError("update: the map is %dx%d, the new texels are %dx%d (the size cannot change)" % (self.width, self.height, new.width, new.height))
-            self.data[...] = new.data
-            self._jl[...] = new._jl
-            for name in self._TABLES:
-                getattr(self.distribution, name)[...] = getattr(new.distribution, name)
-            self.distribution.marginal_func_int = new.distribution.marginal_func_int
+            self._sky = None        # a pending sky is overwritten, not baked
+            self._assign(new._data, new._distribution, new._jl)
         if rot is not None:
             self.rotation = rot.copy()
 
     def record(self):
         r = A.hk_envmap()
-        D = self.distribution
+        D = self.distribution       # (bakes a pending sky)
         r.width, r.height = self.width, self.height
         r.data = self._jl.ctypes.data_as(A.PF)
         r.rotation[:] = [float(x) for x in self.rotation.reshape(-1)]

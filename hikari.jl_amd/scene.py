@@ -386,12 +386,85 @@ class Scene:
             raise ValueError("update_envmap: the map belongs to no EnvironmentLight of this scene")
         rec = self._desc.envmaps[idx]
         rec.rotation[:] = [float(x) for x in env_map.rotation.reshape(-1)]
-        rec.marginal_func_int = float(env_map.distribution.marginal_func_int)
+        if env_map._sky is None:                            # (a sky the host has not baked: _bake_skies refreshes the value)
+            rec.marginal_func_int = float(env_map.distribution.marginal_func_int)
         rot = np.ascontiguousarray(env_map.rotation, dtype=f32) if rotation is not None else None
         from . import _lib
         for h in (getattr(self, "_device", None) or {}).values():
             _lib.check(_lib.lib().hk_scene_update_envmap(h, idx, env_map._jl.ctypes.data_as(A.PF) if data is not None else None,
                                                         rot.ctypes.data_as(A.PF) if rot is not None else None), "hk_scene_update_envmap")
+
+    def update_sky(self, env_light, direction, turbidity=2.5, intensity=None, ground_albedo=None, ground_enabled=True, sun=None, build="device"):
+        """The map of `env_light` (an EnvironmentLight of this scene, as sunsky_to_envlight returns it) becomes the Hosek-Wilkie sky of a
+        new sun `direction` (pointing TO the sun, z up), `turbidity` and ground; its size and rotation stay.
+        build="device": every device scene bakes the texels itself from a parameter record of 1224 bytes (hk_scene_update_envmap_sky)
+        and builds its tables from them.  The map keeps the parameters; its host texels and tables (env_map.data, .distribution) are
+        baked only when something asks for them — reading either, record(), or creating a device scene from the kept description.
+        build="host": the texels are baked here (sunsky.sky_texels) and go through update_envmap.
+        `intensity`: the light's scale becomes the one sunsky_to_envlight gives that intensity.  `sun`: that SunLight of the scene is
+        turned to the new direction as well (with `intensity`, it also gets the spectrum and scale sunsky_to_envlight gives it); both
+        records go through update_light.
+        LATER SCENES.  A device scene created afterwards from the kept description holds the HOST bake.  That is the same sky within
+        the bound recorded in tests/golden/sky_bake_bounds.json (the device and NumPy differ in the last places of cos, acos and exp),
+        not bit for bit the sky of the scene that was edited.  Use build="host" where every scene must hold the same bits.
+        Raises ValueError for what the library would refuse."""
+        from . import sunsky
+        from .envmap import EnvironmentLight
+        from .lights import SunLight
+        if build not in ("device", "host"):
+            raise ValueError("update_sky: build is 'device' or 'host', not %r" % (build,))
+        if not isinstance(env_light, EnvironmentLight) or not any(l is env_light for l in self.lights):
+            raise ValueError("update_sky: env_light is not an EnvironmentLight of this scene")
+        if sun is not None and (not isinstance(sun, SunLight) or not any(l is sun for l in self.lights)):
+            raise ValueError("update_sky: sun is not a SunLight of this scene")
+        env_map = env_light.env_map
+        if env_map.height != env_map.width:
+            raise ValueError("update_sky: the map is %dx%d (a sky is baked into a square map)" % (env_map.width, env_map.height))
+        d = np.asarray(direction, dtype=np.float64).reshape(-1)
+        if d.shape != (3,) or not np.isfinite(d).all() or not (d * d).sum() > 0:
+            raise ValueError("update_sky: the direction is not a finite, non-zero 3-vector")
+        if not np.isfinite(float(turbidity)) or (intensity is not None and not np.isfinite(float(intensity))):
+            raise ValueError("update_sky: non-finite turbidity or intensity")
+        if ground_albedo is not None and not np.isfinite(np.asarray(ground_albedo.c, dtype=np.float64)).all():
+            raise ValueError("update_sky: non-finite ground albedo")
+        sky = dict(direction=tuple(float(x) for x in d), turbidity=float(turbidity), ground_albedo=ground_albedo, ground_enabled=bool(ground_enabled))
+        params = sunsky.sky_params(**sky)
+        if not all(np.isfinite(np.ctypeslib.as_array(getattr(params, name))).all() for name in ("sun_dir", "ground_rgb", "config", "radiance", "xyz_weight")):
+            raise ValueError("update_sky: the cooked coefficients are not finite (turbidity %r)" % (turbidity,))
+        idx = None
+        if self._desc is not None:
+            for idx, e in enumerate(self._envmaps):
+                if e is env_map:
+                    break
+            else:
+                raise ValueError("update_sky: the map belongs to no EnvironmentLight of this scene")
+        if build == "host":
+            self.update_envmap(env_map, data=sunsky.sky_texels(resolution=env_map.height, **sky))
+        else:
+            env_map.set_sky(**sky)
+            if idx is not None:
+                from . import _lib
+                for h in (getattr(self, "_device", None) or {}).values():
+                    _lib.check(_lib.lib().hk_scene_update_envmap_sky(h, idx, C.byref(params)), "hk_scene_update_envmap_sky")
+        pairs = []
+        if intensity is not None:
+            env_light.scale_rgb = env_light.i = sunsky.sky_scale(intensity)
+            pairs.append((next(k for k, l in enumerate(self.lights) if l is env_light), env_light))
+        if sun is not None:
+            new = sunsky.sun_light(sky["direction"], 1.0 if intensity is None else intensity)
+            sun.direction = new.direction
+            if intensity is not None:
+                sun.i, sun.scale = new.i, new.scale
+            pairs.append((next(k for k, l in enumerate(self.lights) if l is sun), sun))
+        if pairs:
+            self._replace_lights(pairs)
+
+    def _bake_skies(self):
+        """The host bakes update_sky(build="device") left pending, into the arrays the kept description points to."""
+        for idx, e in enumerate(self._envmaps):
+            if e._sky is not None:
+                e.bake()
+                self._desc.envmaps[idx].marginal_func_int = float(e.distribution.marginal_func_int)
 
     def update_medium(self, medium, **changes):
         """New volume data, coefficients, bounds or transform for a medium of this scene (the keywords of the medium's own update()),
@@ -782,13 +855,20 @@ class Scene:
         except Exception:
             pass
 
-    @property
-    def desc(self):
+    def _description(self, bake_skies=True):
+        """The kept description, complete: stale media records refilled, pending sky bakes run.  bake_skies=False is for a reader that
+        follows no environment-map pointer (volpath.scene_handle with a device scene in hand)."""
         if self._desc is None:
             self.sync()
         if self._stale_media:
             self._refresh_media()
+        if bake_skies:
+            self._bake_skies()
         return self._desc
+
+    @property
+    def desc(self):
+        return self._description()
 
     def world_radius(self):
         self.desc

@@ -122,7 +122,9 @@ class _Options:
 
 
 def scene_handle(ctx, scene):
-    d = scene.desc
+    # (a scene that already has its device scene here is not asked to bake a sky update_sky left to the device: Scene._description)
+    have = id(ctx) in (getattr(scene, "_device", None) or {})
+    d = scene._description(bake_skies=False) if have else scene.desc
     dev = getattr(scene, "_device", None)
     if dev is None:
         dev = scene._device = {}

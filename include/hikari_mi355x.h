@@ -480,6 +480,50 @@ typedef struct hk_dense_field {
 } hk_dense_field;
 int32_t hk_scene_update_medium_dense(hk_scene* scene, int32_t idx, const hk_medium* medium, const hk_dense_field* field);
 
+/* hk_scene_update_envmap_sky: the texels of environment map `idx` become a Hosek-Wilkie sky (lights/sun_sky.jl:87-190, 319-434), evaluated
+ * ON THE DEVICE from the record below, one thread per texel; the Distribution2D tables are then rebuilt from them exactly as
+ * hk_scene_update_envmap rebuilds them.  Only the record crosses to the device (1224 bytes against 16 * res^2 of texels).  The caller
+ * cooks the coefficients for its turbidity, albedo and solar elevation (hosek_cook_config / hosek_cook_radiance, a few hundred flops):
+ * the library holds no dataset.  Like hk_scene_update_envmap with texels, the call renders the noted calls first, joins the lanes and
+ * enqueues on the context's stream; it does not wait for the device, clears no film and leaves `rotation` alone.
+ * Texel (v_idx, u_idx) (0-based; hk_envmap::data[v_idx + height * u_idx]) of a map of res x res.  binary32 where marked f32, binary64
+ * elsewhere, nothing contracted, division and square root correctly rounded:
+ *   direction  f32: c(k) = ((float)(k + 1) - 0.5f) / (float)res;  w = equal_area_square_to_sphere(c(u_idx), c(v_idx))
+ *              (textures/environment_map.jl:131-160); cos and sin of phi are taken in double and rounded to binary32
+ *   ground     ground_enabled != 0 and w.z <= 0 (+0 included): the texel is (ground_rgb, 1)
+ *   angles     f32: cosg = clamp((w.x*d.x + w.y*d.y) + w.z*d.z, -1, 1), d = sun_dir;  theta = acos(clamp(w.z, 0, 1)) and
+ *              gamma = acos(cosg) are binary32 values (acos taken in double and rounded), widened to double;
+ *              cg = cos(gamma), ct = max(cos(theta), 0)
+ *   band b     c = config[b]:  F[b] = (1 + c0*exp(c1 / (ct + 0.01))) * (c2 + c3*exp(c4*gamma) + c5*cg*cg
+ *                                     + c6*(1 + cg*cg) / (1 + c8*c8 - 2*c8*cg)^1.5 + c7*sqrt(ct)),    x^1.5 taken as x * sqrt(x)
+ *   lambda_k   = 320 + k*400/12 (k = 0 .. 12), x = (lambda_k - 320) / 40, low = floor(x), t = x - low:
+ *              L[k] = F[low]*radiance[low] when t < 1e-6, otherwise
+ *              L[k] = (1 - t)*(F[low]*radiance[low]) + (low + 1 < 11 ? t*F[low+1]*radiance[low+1] : 0)
+ *   colour     XYZ[c] = sum over k ascending of L[k] * xyz_weight[c][k], rounded once to binary32; then in f32, left to right,
+ *              r =  3.2404542f*X - 1.5371385f*Y - 0.4985314f*Z,  g = -0.9692660f*X + 1.8760108f*Y + 0.0415560f*Z,
+ *              b =  0.0556434f*X - 0.2040259f*Y + 1.0572252f*Z;  texel = (max(0, r), max(0, g), max(0, b), 1)
+ * A bake of the same record on another libm (NumPy on the host) differs in the last places: tests/golden/sky_bake_bounds.json records by
+ * how much.  Refused, each with HK_ERR_INVALID and a message, nothing changed: a null scene or null params, idx out of range, a map that
+ * is not square, a map whose tables are not of its texels' resolution, a non-finite entry anywhere in the record, a sun_dir whose squared
+ * length is outside 1 +- 1e-3, reserved != 0.
+ * hk_scene_envmap_copy reads back what the device holds of map `idx`: the sizes, the texels (4 floats per texel, layout of
+ * hk_envmap::data) and the Distribution2D tables in the layouts of the hk_envmap record with nu = width and nv = height
+ * (marginal_func_int: one float).  Any output pointer may be NULL.  It waits for the device.  Refused: a null scene, idx out of range,
+ * a table pointer for a map whose tables are not of its texels' resolution (the caller sizes its buffers from width and height; the
+ * sizes, the texels and marginal_func_int of such a map can still be read). */
+typedef struct hk_sky_params {
+    float   sun_dir[3];          /* unit vector TO the sun in the map's own frame (before `rotation`), z up */
+    int32_t ground_enabled;
+    float   ground_rgb[3];       /* the texel of every direction with z <= 0 when ground_enabled */
+    int32_t reserved;            /* 0 */
+    double  config[11][9];       /* cooked Hosek-Wilkie coefficients per band (hosek_cook_config) */
+    double  radiance[11];        /* cooked band radiances (hosek_cook_radiance) */
+    double  xyz_weight[3][13];   /* spectrum -> XYZ weights of the 13 wavelengths, / CIE_Y_INTEGRAL */
+} hk_sky_params;
+int32_t hk_scene_update_envmap_sky(hk_scene* scene, int32_t idx, const hk_sky_params* sky);
+int32_t hk_scene_envmap_copy(hk_scene* scene, int32_t idx, int32_t* width, int32_t* height, float* texels /* 4 per texel in the layout of hk_envmap::data */,
+                             float* conditional_func, float* conditional_cdf, float* marginal_func, float* marginal_cdf, float* marginal_func_int);
+
 int32_t hk_integrator_create(hk_ctx* ctx, const hk_integrator_params* params, hk_integrator** out);
 int32_t hk_integrator_destroy(hk_integrator* integ);
 
@@ -503,7 +547,7 @@ int32_t hk_film_clear(hk_film* film); /* clear!(vp), volpath.jl:108-113 */
  *     following on) are rendered as ONE pass — bit-identical film, a seventh of the time — when the note reaches HK_BATCH_PATHS_M
  *     (64 M paths), when a call comes that does not continue it, or when anything looks: hk_flush, hk_sync, every hk_film_* / hk_stats_* /
  *     hk_*_destroy / hk_ctx_set_option /
- *     hk_scene_set_transform / hk_scene_set_vertices / hk_scene_update_materials / hk_scene_update_lights / hk_scene_update_envmap / hk_scene_update_medium / hk_scene_update_medium_dense entry point.  hk_flush enqueues the noted calls without waiting for them.
+ *     hk_scene_set_transform / hk_scene_set_vertices / hk_scene_update_materials / hk_scene_update_lights / hk_scene_update_envmap / hk_scene_update_medium / hk_scene_update_medium_dense / hk_scene_update_envmap_sky entry point.  hk_flush enqueues the noted calls without waiting for them.
  *     HK_BATCH_PATHS_M=0 (hk_ctx_set_option) turns the noting off.
  * Argument errors are reported by the call itself; a device error of a deferred pass by the call that flushes it — also by the
  * destroy entry points, which still destroy their object. */

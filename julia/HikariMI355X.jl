@@ -769,6 +769,63 @@ function medium_tree(vp::MI355XVolPath, index::Integer)
     bytes, table, dims, tmin
 end
 
+# hk_sky_params of the header (C arrays are row-major: config[b][j] is entry 9b + j + 1, xyz_weight[c][k] entry 13c + k + 1)
+struct SkyParamsRecord
+    sun_dir::NTuple{3,Float32}
+    ground_enabled::Int32
+    ground_rgb::NTuple{3,Float32}
+    reserved::Int32
+    config::NTuple{99,Float64}
+    radiance::NTuple{11,Float64}
+    xyz_weight::NTuple{39,Float64}
+end
+
+"""
+    update_sky!(vp, index; direction, turbidity = 2.5f0, ground_albedo = Hikari.RGBSpectrum(0.3f0), ground_enabled = true)
+
+The texels of environment map `index` (0-based) of the scene on the devices become the Hosek-Wilkie sky `Hikari.sunsky_to_envlight` bakes
+for the same arguments (`direction` points TO the sun), evaluated on the device: only the cooked coefficients of `Hikari.HosekState`, the
+sun direction, the ground texel and the spectrum -> XYZ weights cross (1224 bytes), and the library builds the `Distribution2D` tables
+from the texels it wrote.  The map must be square; its rotation stays.  The device's texels agree with the host bake within the bound
+recorded in tests/golden/sky_bake_bounds.json, not to the bit.
+"""
+function update_sky!(vp::MI355XVolPath, index::Integer; direction, turbidity = 2.5f0, ground_albedo = Hikari.RGBSpectrum(0.3f0), ground_enabled::Bool = true)
+    dir = Hikari.normalize(Hikari.Vec3f(direction...))
+    state = Hikari.HosekState(Float64(Float32(turbidity)), 0.5, Float64(asin(clamp(dir[3], 0f0, 1f0))))
+    lambdas = [320.0 + i * (720.0 - 320.0) / 12 for i in 0:12]
+    unit(k) = [j == k ? 1.0 : 0.0 for j in 1:13]
+    weights = [Hikari._spectrum_to_xyz(lambdas, unit(k)) for k in 1:13]          # linear in the values: the weight of each wavelength
+    ground = ground_albedo * 0.3f0
+    rec = SkyParamsRecord(tup3(dir), Int32(ground_enabled), (ground.c[1], ground.c[2], ground.c[3]), Int32(0),
+                          ntuple(i -> state.configs[(i - 1) ÷ 9 + 1][(i - 1) % 9 + 1], 99), state.radiances,
+                          ntuple(i -> weights[(i - 1) % 13 + 1][(i - 1) ÷ 13 + 1], 39))
+    for d in vp.devs
+        d.scene == C_NULL && continue
+        check(ccall((:hk_scene_update_envmap_sky, LIB), Int32, (Ptr{Cvoid}, Int32, Ref{SkyParamsRecord}), d.scene, Int32(index), rec), "hk_scene_update_envmap_sky")
+    end
+    nothing
+end
+
+"""
+    envmap_copy(vp, index) -> (texels, conditional_func, conditional_cdf, marginal_func, marginal_cdf, marginal_func_int)
+
+Environment map `index` as the first device holds it (whichever update put it there): the texels as a `4 x height x width` `Float32`
+array (r, g, b, a of `data[y, x]`) and the `Distribution2D` tables in the reference's layouts.  Waits for the device.
+"""
+function envmap_copy(vp::MI355XVolPath, index::Integer)
+    d = first(vp.devs)
+    w, h = Ref{Int32}(0), Ref{Int32}(0)
+    nul = Ptr{Float32}(C_NULL)
+    check(ccall((:hk_scene_envmap_copy, LIB), Int32, (Ptr{Cvoid}, Int32, Ref{Int32}, Ref{Int32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}), d.scene,
+                Int32(index), w, h, nul, nul, nul, nul, nul, nul), "hk_scene_envmap_copy")
+    nu, nv = Int(w[]), Int(h[])                                                   # the library refuses the table pointers below unless nu == width and nv == height
+    texels = zeros(Float32, 4, nv, nu)
+    cf, cc, mf, mc, mfi = zeros(Float32, nu, nv), zeros(Float32, nu + 1, nv), zeros(Float32, nv), zeros(Float32, nv + 1), zeros(Float32, 1)
+    check(ccall((:hk_scene_envmap_copy, LIB), Int32, (Ptr{Cvoid}, Int32, Ref{Int32}, Ref{Int32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}), d.scene,
+                Int32(index), w, h, texels, cf, cc, mf, mc, mfi), "hk_scene_envmap_copy")
+    texels, cf, cc, mf, mc, mfi[1]
+end
+
 """
     set_vertices!(vp, first_tri, positions; normals = nothing, uvs = nothing)
 
