@@ -156,10 +156,10 @@ EXPORTED_SYMBOLS = [
     "hk_film_update_aux", "hk_film_read_aux", "hk_film_present", "hk_film_present_async",
     "hk_scene_update_medium", "hk_scene_medium_copy", "hk_test_medium_bricks", "hk_scene_set_vertices", "hk_scene_bvh_cost", "hk_scene_bvh_copy",
     "hk_scene_bvh_leaves", "hk_scene_rebuild_bvh", "hk_test_queue_counts", "hk_test_tri_geo", "hk_scene_update_medium_dense", "hk_scene_medium_tree_copy",
-    "hk_scene_update_envmap_sky", "hk_scene_envmap_copy",
+    "hk_scene_update_envmap_sky", "hk_scene_envmap_copy", "hk_scene_refit_lights", "hk_test_light_refit_host", "hk_test_light_table_copy",
 ]
 
-# prototypes (argtypes, restype) of the geometry edit, the tree introspection, the dense-field medium update and the sky bake, in the header's order;
+# prototypes (argtypes, restype) of the geometry edit, the tree introspection, the dense-field medium update, the sky bake and the light-BVH refit;
 # _lib.py installs them
 _VP, _I32, _PI32, _PD = C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double)
 PROTOTYPES = {
@@ -172,4 +172,7 @@ PROTOTYPES = {
     "hk_scene_medium_tree_copy": ([_VP, _I32, C.POINTER(hk_medium), C.POINTER(C.c_int64), C.POINTER(C.c_uint8), _PI32, _PI32, C.POINTER(C.c_uint32)], _I32),
     "hk_scene_update_envmap_sky": ([_VP, _I32, C.POINTER(hk_sky_params)], _I32),
     "hk_scene_envmap_copy": ([_VP, _I32, _PI32, _PI32, PF, PF, PF, PF, PF, PF], _I32),
+    "hk_scene_refit_lights": ([_VP, _I32, _PI32, C.POINTER(hk_light)], _I32),
+    "hk_test_light_refit_host": ([C.POINTER(hk_light), _I32, _I32, _PI32, _PI32, C.POINTER(hk_light), _PI32, PF, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)], _I32),
+    "hk_test_light_table_copy": ([_VP, C.POINTER(C.c_uint32)], _I32),
 }

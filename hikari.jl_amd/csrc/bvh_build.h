@@ -62,6 +62,24 @@ struct LightTables {
 };
 void derive_light_tables(const hk_light* lights, int n, LightBVH& bvh, LightTables& out);
 
+// ---- the light-BVH refit (hk_scene_refit_lights; the arithmetic of inner nodes is hk_light_bounds.h) ----
+// The builder's own bounds of one light.  0: an infinite kind, 1: bounded but outside the tree (phi is not > 0), 2: in the tree, and
+// `leaf` is the leaf node build_light_bvh makes of it (light_1based in child1_or_light).
+int light_leaf(const hk_light& l, int light_1based, LightBVHNodeH& leaf);
+// Where the nodes of a built tree lie on the device (sibling-pair order) and what a refit needs to climb it.
+struct LightRefitLayout {
+    int n_entries = 0;                    // device entries: 2 per light of the tree, entry 1 unused; 0: empty tree
+    std::vector<int32_t> entry_of_host;   // per host node
+    std::vector<int32_t> host_of_entry;   // per entry (-1: entry 1)
+    std::vector<int32_t> parent;          // per entry (-1: the root, entry 1)
+    std::vector<int32_t> leaf_entry;      // per light of the scene, 0-based (-1: not in the tree)
+    std::vector<int32_t> level_entries;   // the inner entries grouped by depth: depth d is [level_start[d], level_start[d + 1])
+    std::vector<int32_t> level_start;
+};
+void light_refit_layout(const LightBVH& bvh, LightRefitLayout& out);
+// the host twin of the device refit: n distinct 0-based light indices and their new records (kinds and tree membership unchanged)
+void refit_light_bvh(LightBVH& bvh, LightTables& t, const LightRefitLayout& lay, int n, const int32_t* index, const hk_light* lights);
+
 // sigmoid-polynomial helpers shared by the host-side bakers (spectral/rgb2spec.jl:17-53, 85-167)
 struct RGB2Spec {
     int res = 0;

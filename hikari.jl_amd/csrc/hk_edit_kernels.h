@@ -1,5 +1,6 @@
-// hk_edit_kernels.h — the scene edits: k_slot_of_prim, k_tri_geo, k_xform_tris, k_refit_level, k_set_tris and the tree cost k_bvh_cost.
-// Part of the hk_kernels.hip translation unit (needs hk_device.h and hk_edit_host.h: the arithmetic the host applies to the same arrays).
+// hk_edit_kernels.h — the scene edits: k_slot_of_prim, k_tri_geo, k_xform_tris, k_refit_level, k_set_tris, the light-BVH refit
+// k_light_refit_leaves / k_light_refit_level and the tree cost k_bvh_cost.
+// Part of the hk_kernels.hip translation unit (needs hk_device.h, hk_edit_host.h and hk_light_bounds.h: the arithmetic the host applies to the same arrays).
 #pragma once
 
 // ---------------------------------------------------------------------------------------------------
@@ -224,6 +225,44 @@ __global__ void __launch_bounds__(256) k_set_tris(DSetTris A) {
         tri_geo_store(p, t, A.geo, A.shade);
         float4* L = A.leaf + 3 * (size_t)A.slot_of_prim[t];
         hk_pack_leaf_tri(L, p, L[0].w, L[1].w, L[2].w);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// LIGHT-BVH REFIT (hk_scene_refit_lights): the topology stays, the bounds on the paths from the edited leaves to the root are
+// recomputed with the arithmetic of hk_light_bounds.h.  k_light_refit_leaves gives every edited light to one lane: it puts the baked
+// record in its place, and for a light of the tree writes the raw leaf (the builder's bounds, from the host) and the record the walk
+// reads, then climbs the parent chain storing this call's stamp until it meets it — lanes that meet on a node store the same word, so plain
+// stores do, and the lane that stored first goes on to the root (the kernel boundary before the first level launch publishes every stamp).
+// k_light_refit_level then takes the inner entries of ONE depth, deepest first (the kernel boundary publishes the level below, as
+// for k_refit_level): a stamped entry reads its two children — one 128-byte pair — and writes their union and its walked record.
+// Which lane computes a node never changes what it computes: the result is a function of the tree and the edit alone.
+// ---------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_light_refit_leaves(DLightRefit A) {
+    static_assert(sizeof(DLight) % 16 == 0 && sizeof(HkLightRaw) == 64 && sizeof(HkLightWalk) == sizeof(DLightNode), "record sizes");
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < A.n; i += gridDim.x * blockDim.x) {
+        const int2 sl = A.slot[i];
+        const uint4* src = A.rec + (size_t)i * (sizeof(DLight) / 16);
+        uint4* dst = reinterpret_cast<uint4*>(A.lights + sl.x);
+        for (int k = 0; k < (int)(sizeof(DLight) / 16); ++k) dst[k] = src[k];
+        if (sl.y < 0) continue;
+        const int e = A.leaf_entry[sl.x];
+        if (e < 0) continue;   // (the host refuses an edit that would put a light into the tree)
+        const HkLightRaw leaf = A.leaf[sl.y];
+        A.raw[e] = leaf;
+        *reinterpret_cast<HkLightWalk*>(A.lnodes + e) = hk_lb_walk_record(leaf, leaf.child1_or_light);
+        // an entry that carries this call's stamp has a lane above it that climbs, or has climbed, the rest: N lanes store about 2 N words, not N x depth
+        for (int p = A.parent[e]; p >= 0 && A.stamps[p] != A.stamp; p = A.parent[p]) A.stamps[p] = A.stamp;
+    }
+}
+__global__ void __launch_bounds__(256) k_light_refit_level(const int* __restrict__ entries, int count, DLightRefit A) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
+        const int e = entries[i];
+        if (A.stamps[e] != A.stamp) continue;
+        const uint32_t c = A.lnodes[e].child1_or_light;   // the entry of child 0; child 1 is the next one
+        const HkLightRaw u = hk_lb_union(A.raw[c], A.raw[c + 1]);
+        A.raw[e] = u;
+        *reinterpret_cast<HkLightWalk*>(A.lnodes + e) = hk_lb_walk_record(u, c);
     }
 }
 

@@ -283,6 +283,17 @@ struct hk_scene {
         hipEvent_t ev = nullptr;
     };
     std::vector<Staging> staging;
+    // ---- hk_scene_refit_lights: what a refit of the light BVH needs besides lnodes, filled from `lbvh` at the scene's FIRST refit
+    // (a scene that is never refit pays nothing).  While `ready`, the tree lives on the device: `lbvh` keeps the topology and the
+    // trails, its bounds are those of the last build (hk_scene_light_bvh_copy reads `raw` back).  hk_scene_update_lights rebuilds
+    // and clears `ready`; the buffers are sized by the light count and stay.
+    struct LightRefit {
+        bool ready = false;
+        hk::LightRefitLayout lay;
+        DevBuf raw, parent, leaf_entry, level_entries, stamps;   // per entry: the node as built (bmin bmax w phi cos_o cos_e bits), its parent, its stamp; per light its leaf entry; the inner entries by depth
+        DevBuf stage;                                            // one call's records, leaves and slots (sized for an edit of every light)
+        uint32_t stamp = 0;
+    } lrefit;
     // ---- hk_scene_update_medium: per medium, the record as created / last updated (what an update is checked against; its pointers
     // only say which arrays were given and are never followed), the device record as uploaded, and the buffers (in `owned`) it points into
     struct Medium {

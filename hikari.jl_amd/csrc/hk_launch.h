@@ -54,6 +54,10 @@ void launch_xform_tris(hipStream_t s, const DXform& X, int first, int n, const f
 void launch_refit_level(hipStream_t s, int begin, int end, DNode* nodes, DQNode* qnodes, const DQGrid& grid, const float4* leaf, const float* pos);
 // hk_scene_set_vertices: one pass over the uploaded range (base copies, transform, every copy of the geometry, leaf slots)
 void launch_set_tris(hipStream_t s, const DSetTris& A);
+// hk_scene_refit_lights: the edited records and leaves into place (one lane per edited light), then the stamped inner entries of one
+// depth of the light BVH (`entries`: that depth's slice of the scene's list), called deepest depth first
+void launch_light_refit_leaves(hipStream_t s, const DLightRefit& A);
+void launch_light_refit_level(hipStream_t s, const int* entries, int count, const DLightRefit& A);
 // hk_scene_bvh_cost: partial[b] = the cost terms of nodes [256 b, 256 b + 256) (bvh_cost_blocks(n) of them)
 inline int bvh_cost_blocks(int n_nodes) { return (n_nodes + 255) / 256; }
 void launch_bvh_cost(hipStream_t s, const DNode* nodes, int n, double* partial);

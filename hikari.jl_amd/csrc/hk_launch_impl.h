@@ -460,6 +460,10 @@ void launch_refit_level(hipStream_t s, int begin, int end, DNode* nodes, DQNode*
     hipLaunchKernelGGL(k_refit_level, dim3(grid_for(end - begin, 256, 8192)), dim3(256), 0, s, begin, end, nodes, qnodes, grid, leaf, pos);
 }
 void launch_set_tris(hipStream_t s, const DSetTris& A) { hipLaunchKernelGGL(k_set_tris, dim3(grid_for(A.n, 256, 8192)), dim3(256), 0, s, A); }
+void launch_light_refit_leaves(hipStream_t s, const DLightRefit& A) { hipLaunchKernelGGL(k_light_refit_leaves, dim3(grid_for(A.n, 256, 8192)), dim3(256), 0, s, A); }
+void launch_light_refit_level(hipStream_t s, const int* entries, int count, const DLightRefit& A) {
+    hipLaunchKernelGGL(k_light_refit_level, dim3(grid_for(count, 256, 8192)), dim3(256), 0, s, entries, count, A);
+}
 void launch_bvh_cost(hipStream_t s, const DNode* nodes, int n, double* partial) {
     hipLaunchKernelGGL(k_bvh_cost, dim3((unsigned)bvh_cost_blocks(n)), dim3(256), 0, s, nodes, n, partial);
 }

@@ -831,9 +831,25 @@ extern "C" int32_t hk_scene_bvh_info(hk_scene* s, int32_t* n_nodes, int32_t* n_l
 extern "C" int32_t hk_scene_light_bvh_copy(hk_scene* s, int32_t* n_nodes, float* nodes_out, uint32_t* bit_trails) {
     if (!s || !n_nodes) return fail(HK_ERR_INVALID, "null argument");
     *n_nodes = (int32_t)s->lbvh.nodes.size();
+    // after hk_scene_refit_lights the bounds live on the device: read them back (this waits for the context's stream) and hand them
+    // out in the host order, with the topology words of the tree as built
+    std::vector<hk::LightBVHNodeH> refit;
+    if (nodes_out && s->lrefit.ready && !s->lbvh.nodes.empty()) {
+        hk_ctx* c = s->ctx;
+        HIP_TRY(hipSetDevice(c->device));
+        std::vector<hk::LightBVHNodeH> raw((size_t)s->lrefit.lay.n_entries);
+        HIP_TRY(hipMemcpyAsync(raw.data(), s->lrefit.raw.p, raw.size() * sizeof(hk::LightBVHNodeH), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        refit.resize(s->lbvh.nodes.size());
+        for (size_t i = 0; i < refit.size(); ++i) {
+            refit[i] = raw[(size_t)s->lrefit.lay.entry_of_host[i]];
+            refit[i].bits = (refit[i].bits & 1u) | (s->lbvh.nodes[i].bits & 2u);
+            refit[i].child1_or_light = s->lbvh.nodes[i].child1_or_light;
+        }
+    }
     if (nodes_out)
         for (size_t i = 0; i < s->lbvh.nodes.size(); ++i) {
-            const hk::LightBVHNodeH& n = s->lbvh.nodes[i];
+            const hk::LightBVHNodeH& n = refit.empty() ? s->lbvh.nodes[i] : refit[i];
             float* o = nodes_out + 16 * i;
             std::memcpy(o, n.bmin, 12);
             std::memcpy(o + 3, n.bmax, 12);

@@ -7,6 +7,7 @@
 // device); hk_scene_bvh_cost / hk_scene_bvh_copy / hk_scene_bvh_leaves read the tree back, hk_scene_medium_tree_copy a NanoVDB tree.
 #include "hk_host.h"
 #include "hk_bvh_decide.h"
+#include "hk_light_bounds.h"
 
 // ---- in-place scene edits -----------------------------------------------------------------------------------------------------
 // Only hk_scene_rebuild_bvh and hk_scene_update_medium_dense wait for the device, once each and for a small record.  For every
@@ -293,8 +294,134 @@ extern "C" int32_t hk_scene_update_lights(hk_scene* s, int32_t first, int32_t n,
     HIP_TRY(hipEventRecord(st->ev, c->stream));
     s->h_lights.swap(all);
     s->lbvh = std::move(lbvh);
+    s->lrefit.ready = false;   // the refit arrays described the tree that was: the next refit fills them from the new one
     s->d.num_bvh_lights = t.num_bvh;
     s->d.num_infinite_lights = t.num_infinite;
+    return HK_OK;
+}
+
+// ---- hk_scene_refit_lights: new records for a SET of lights, the light BVH refit on the device (the header states the contract) ----
+// What the edit leaves valid, beyond what hk_scene_update_lights argues at the head of this file: the topology, so the bit trails, the
+// child entries of lnodes, num_bvh_lights, num_infinite_lights and the infinite list — a light may not enter or leave the tree.  The
+// readers of lnodes (bvh_sample_light / bvh_pmf of hk_device.h, k_light_select and k_light_select_pool with its LDS copy of the top of
+// the tree, k_shade, k_small_pass, hk_test_light_bvh) take every node from the table at launch and hold nothing across calls.
+namespace {
+// the refit arrays of a scene, from the tree as built (first refit, and the first after a rebuild)
+int ensure_light_refit(hk_scene* s) {
+    hk_scene::LightRefit& R = s->lrefit;
+    if (R.ready) return HK_OK;
+    hk_ctx* c = s->ctx;
+    hk::light_refit_layout(s->lbvh, R.lay);
+    const size_t NL = s->h_lights.size(), cap = light_table_capacity((int)NL), E = (size_t)R.lay.n_entries, n_inner = R.lay.level_entries.size();
+    if (E > 2 * cap || n_inner > cap) return fail(HK_ERR_UNSUPPORTED, "hk_scene_refit_lights: the light tree exceeds the scene's capacity");
+    if (!R.raw.p) {   // sized by the light count, as lnodes is: a rebuild changes the tree, never the capacity
+        HIP_TRY(R.raw.alloc(2 * cap * sizeof(HkLightRaw)));
+        HIP_TRY(R.parent.alloc(2 * cap * 4));
+        HIP_TRY(R.stamps.alloc(2 * cap * 4));
+        HIP_TRY(R.leaf_entry.alloc(cap * 4));
+        HIP_TRY(R.level_entries.alloc(cap * 4));
+        HIP_TRY(R.stage.alloc(cap * (sizeof(DLight) + sizeof(HkLightRaw) + sizeof(int2))));   // the largest edit: no call ever grows it (growing would wait for the device)
+    }
+    const size_t b_raw = E * sizeof(HkLightRaw), b_par = E * 4, b_leaf = NL * 4, b_lev = n_inner * 4;
+    hk_scene::Staging* st = nullptr;
+    if (int e = acquire_staging(s, b_raw + b_par + b_leaf + b_lev + 16, st)) return e;
+    char* h = static_cast<char*>(st->host);
+    std::memset(h, 0, b_raw);
+    for (size_t e = 0; e < E; ++e)
+        if (R.lay.host_of_entry[e] >= 0) std::memcpy(h + e * sizeof(HkLightRaw), &s->lbvh.nodes[(size_t)R.lay.host_of_entry[e]], sizeof(HkLightRaw));
+    std::memcpy(h + b_raw, R.lay.parent.data(), b_par);
+    std::memcpy(h + b_raw + b_par, R.lay.leaf_entry.data(), b_leaf);
+    std::memcpy(h + b_raw + b_par + b_leaf, R.lay.level_entries.data(), b_lev);
+    if (b_raw) HIP_TRY(hipMemcpyAsync(R.raw.p, h, b_raw, hipMemcpyHostToDevice, c->stream));
+    if (b_par) HIP_TRY(hipMemcpyAsync(R.parent.p, h + b_raw, b_par, hipMemcpyHostToDevice, c->stream));
+    if (b_leaf) HIP_TRY(hipMemcpyAsync(R.leaf_entry.p, h + b_raw + b_par, b_leaf, hipMemcpyHostToDevice, c->stream));
+    if (b_lev) HIP_TRY(hipMemcpyAsync(R.level_entries.p, h + b_raw + b_par + b_leaf, b_lev, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(R.stamps.p, 0, 2 * cap * 4, c->stream));
+    HIP_TRY(hipEventRecord(st->ev, c->stream));
+    R.stamp = 0;
+    R.ready = true;
+    return HK_OK;
+}
+bool floats_finite(const float* v, int n) {
+    for (int k = 0; k < n; ++k)
+        if (!std::isfinite(v[k])) return false;
+    return true;
+}
+}  // namespace
+
+extern "C" int32_t hk_scene_refit_lights(hk_scene* s, int32_t n, const int32_t* index, const hk_light* lights) {
+    static_assert(sizeof(HkLightRaw) == sizeof(hk::LightBVHNodeH), "a raw node is the builder's node");
+    if (!s || !index || !lights) return fail(HK_ERR_INVALID, "hk_scene_refit_lights: null argument");
+    const int NL = (int)s->h_lights.size();
+    if (n < 1 || n > NL) return fail(HK_ERR_INVALID, "hk_scene_refit_lights: the number of lights is outside the scene");
+    std::vector<char> seen((size_t)NL, 0);
+    std::vector<hk::LightBVHNodeH> leaves;
+    std::vector<int2> slot((size_t)n);
+    for (int j = 0; j < n; ++j) {   // hk_scene_update_lights' checks, and what keeps the topology valid
+        const int idx = index[j];
+        auto at = [idx]() { return "hk_scene_refit_lights: light " + std::to_string(idx) + ": "; };   // (built only for a refusal)
+        if (idx < 0 || idx >= NL) return fail(HK_ERR_INVALID, at() + "index outside the scene");
+        if (seen[(size_t)idx]) return fail(HK_ERR_INVALID, at() + "the index is given twice");
+        seen[(size_t)idx] = 1;
+        const hk_light& l = lights[j];
+        if (l.kind != s->h_lights[(size_t)idx].kind) return fail(HK_ERR_INVALID, at() + "the kind differs from the record it replaces");
+        if (l.kind == HK_LIGHT_ENVIRONMENT && (l.envmap < 0 || l.envmap >= (int)s->h_envmaps.size())) return fail(HK_ERR_INVALID, at() + "environment light refers to a missing envmap");
+        if (l.kind == HK_LIGHT_DIFFUSE_AREA && l.Le.tex >= s->n_textures) return fail(HK_ERR_INVALID, at() + "area light: Le texture index out of range");
+        if ((l.kind == HK_LIGHT_POINT || l.kind == HK_LIGHT_SPOT) && !floats_finite(l.position, 3)) return fail(HK_ERR_INVALID, at() + "non-finite position");
+        if (l.kind == HK_LIGHT_DIFFUSE_AREA && !(floats_finite(l.v, 9) && floats_finite(l.normal, 3) && std::isfinite(l.area))) return fail(HK_ERR_INVALID, at() + "non-finite vertex, normal or area");
+        hk::LightBVHNodeH leaf;
+        const bool in_tree = hk::light_leaf(l, idx + 1, leaf) == 2, was = s->lbvh.bit_trails[(size_t)idx] != 0xFFFFFFFFu;
+        if (in_tree != was)
+            return fail(HK_ERR_INVALID, at() + (in_tree ? "the light would enter the light tree" : "the light would leave the light tree") +
+                                            " (bounded lights of positive power are in it): a refit keeps the topology, send this edit with hk_scene_update_lights");
+        slot[(size_t)j] = make_int2(idx, in_tree ? (int)leaves.size() : -1);
+        if (in_tree) {
+            if (!(floats_finite(leaf.bmin, 3) && floats_finite(leaf.bmax, 3) && floats_finite(leaf.w, 3) && std::isfinite(leaf.phi) && std::isfinite(leaf.cos_o) && std::isfinite(leaf.cos_e)))
+                return fail(HK_ERR_INVALID, at() + "non-finite light bounds (direction, cone or power)");
+            leaves.push_back(leaf);
+        }
+    }
+    hk_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    KnobScope knobs(&c->knobs);
+    hk_scene::LightRefit& R = s->lrefit;
+    // one staging block, proportional to the edit: the n baked records, the raw leaves, the slots
+    const size_t b_rec = (size_t)n * sizeof(DLight), b_leaf = leaves.size() * sizeof(HkLightRaw), b_slot = (size_t)n * sizeof(int2), total = b_rec + b_leaf + b_slot;
+    if (int e = ensure_light_refit(s)) return e;                // new arrays only: the scene's tables are as they were
+    hk_scene::Staging* st = nullptr;
+    if (int e = acquire_staging(s, total, st)) return e;
+    if (int e = join_lanes(c)) return e;   // noted calls render the old lights; the lanes finish before the stream rewrites them
+    char* h = static_cast<char*>(st->host);
+    DLight* rec = reinterpret_cast<DLight*>(h);
+    std::memset(rec, 0, b_rec);
+    for (int j = 0; j < n; ++j) bake_light(c->r2s_host, lights[j], rec[j]);
+    if (b_leaf) std::memcpy(h + b_rec, leaves.data(), b_leaf);
+    std::memcpy(h + b_rec + b_leaf, slot.data(), b_slot);
+    char* dv = R.stage.as<char>();
+    HIP_TRY(hipMemcpyAsync(dv, h, total, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipEventRecord(st->ev, c->stream));
+    if (++R.stamp == 0) {   // the stamps have gone round: none may look like this call's
+        HIP_TRY(hipMemsetAsync(R.stamps.p, 0, R.stamps.bytes, c->stream));
+        R.stamp = 1;
+    }
+    DLightRefit A{};
+    A.n = n, A.stamp = R.stamp;
+    A.rec = reinterpret_cast<const uint4*>(dv);
+    A.leaf = reinterpret_cast<const HkLightRaw*>(dv + b_rec);
+    A.slot = reinterpret_cast<const int2*>(dv + b_rec + b_leaf);
+    A.lights = s->lights.as<DLight>();
+    A.raw = R.raw.as<HkLightRaw>();
+    A.lnodes = s->lnodes.as<DLightNode>();
+    A.parent = R.parent.as<int>(), A.leaf_entry = R.leaf_entry.as<int>(), A.stamps = R.stamps.as<uint32_t>();
+    hk::launch_light_refit_leaves(c->stream, A);
+    HIP_TRY(hipGetLastError());
+    if (!leaves.empty())
+        for (int d = (int)R.lay.level_start.size() - 2; d >= 0; --d) {   // nothing to do when the root is a leaf
+            const int begin = R.lay.level_start[(size_t)d], count = R.lay.level_start[(size_t)d + 1] - begin;
+            hk::launch_light_refit_level(c->stream, R.level_entries.as<int>() + begin, count, A);
+            HIP_TRY(hipGetLastError());
+        }
+    for (int j = 0; j < n; ++j) s->h_lights[(size_t)index[j]] = lights[j];
     return HK_OK;
 }
 

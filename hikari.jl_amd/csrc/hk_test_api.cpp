@@ -131,6 +131,56 @@ extern "C" int32_t hk_test_light_bvh(hk_ctx* c, hk_scene* sc, int32_t n, const f
     return HK_OK;
 }
 
+// The host twin of hk_scene_refit_lights (hk::refit_light_bvh) on a tree built from `lights`: no device, no context.  The calls are
+// applied in turn; call k takes the next call_n[k] entries of index / records.
+extern "C" int32_t hk_test_light_refit_host(const hk_light* lights, int32_t n_lights, int32_t n_calls, const int32_t* call_n, const int32_t* index, const hk_light* records,
+                                            int32_t* n_nodes, float* nodes_out, uint32_t* bit_trails, uint32_t* table_out) {
+    if (!lights || n_lights < 1 || n_calls < 0 || (n_calls > 0 && (!call_n || !index || !records)) || !n_nodes) return fail(HK_ERR_INVALID, "hk_test_light_refit_host: bad argument");
+    std::vector<hk_light> all(lights, lights + n_lights);
+    hk::LightBVH bvh;
+    hk::LightTables t;
+    hk::derive_light_tables(all.data(), n_lights, bvh, t);
+    hk::LightRefitLayout lay;
+    hk::light_refit_layout(bvh, lay);
+    size_t at = 0;
+    for (int k = 0; k < n_calls; ++k) {
+        for (int j = 0; j < call_n[k]; ++j) {
+            const int idx = index[at + (size_t)j];
+            hk::LightBVHNodeH leaf;
+            if (idx < 0 || idx >= n_lights || records[at + (size_t)j].kind != all[(size_t)idx].kind ||
+                (hk::light_leaf(records[at + (size_t)j], idx + 1, leaf) == 2) != (bvh.bit_trails[(size_t)idx] != 0xFFFFFFFFu))
+                return fail(HK_ERR_INVALID, "hk_test_light_refit_host: an edit hk_scene_refit_lights refuses");
+        }
+        hk::refit_light_bvh(bvh, t, lay, call_n[k], index + at, records + at);
+        for (int j = 0; j < call_n[k]; ++j) all[(size_t)index[at + (size_t)j]] = records[at + (size_t)j];
+        at += (size_t)call_n[k];
+    }
+    *n_nodes = (int32_t)bvh.nodes.size();
+    if (nodes_out)
+        for (size_t i = 0; i < bvh.nodes.size(); ++i) {   // hk_scene_light_bvh_copy's record
+            const hk::LightBVHNodeH& n = bvh.nodes[i];
+            float* o = nodes_out + 16 * i;
+            std::memcpy(o, n.bmin, 12), std::memcpy(o + 3, n.bmax, 12), std::memcpy(o + 6, n.w, 12);
+            o[9] = n.phi, o[10] = n.cos_o, o[11] = n.cos_e;
+            o[12] = (n.bits & 1u) ? 1.0f : 0.0f, o[13] = (float)n.child1_or_light, o[14] = (n.bits & 2u) ? 1.0f : 0.0f, o[15] = 0.0f;
+        }
+    if (bit_trails) std::memcpy(bit_trails, bvh.bit_trails.data(), bvh.bit_trails.size() * 4);
+    if (table_out) {   // the walked table at the capacity of the scene: 2 n_lights entries, the rest zero
+        std::memset(table_out, 0, 2 * (size_t)n_lights * sizeof(hk::LightNodeRec));
+        std::memcpy(table_out, t.nodes.data(), t.nodes.size() * sizeof(hk::LightNodeRec));
+    }
+    return HK_OK;
+}
+// the table the light sampler walks, as the device holds it now: 16 words per entry, 2 max(n_lights, 1) entries (waits for the stream)
+extern "C" int32_t hk_test_light_table_copy(hk_scene* sc, uint32_t* table_out) {
+    if (!sc || !table_out) return fail(HK_ERR_INVALID, "null argument");
+    hk_ctx* c = sc->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(table_out, sc->lnodes.p, 2 * light_table_capacity((int)sc->h_lights.size()) * sizeof(DLightNode), hipMemcpyDeviceToHost));
+    return HK_OK;
+}
+
 extern "C" int32_t hk_test_mix(hk_ctx* c, hk_scene* sc, int32_t mat_idx, int32_t n, const float* p3, const float* wo3, const float* uv2, int32_t* out_mat) {
     if (!c || !sc || !p3 || !wo3 || !uv2 || !out_mat) return fail(HK_ERR_INVALID, "null argument");
     if (mat_idx < 0 || mat_idx >= sc->n_materials) return fail(HK_ERR_INVALID, "material index out of range");

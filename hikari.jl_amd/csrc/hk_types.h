@@ -272,6 +272,25 @@ struct DSetTris {
     float4* leaf;
 };
 
+// hk_scene_refit_lights: the arguments of k_light_refit_leaves / k_light_refit_level.  rec / slot / leaf are the staged edit: n baked
+// records, per record {flat light index, its staged leaf or -1 for a light outside the tree}, and the raw leaves (the builder's
+// bounds of the new records, computed on the host).  raw / parent / leaf_entry / stamps are the scene's refit arrays, in the entry
+// order of lnodes (hk_light_bounds.h has the two node layouts).
+struct HkLightRaw;
+struct DLightRefit {
+    int n;
+    uint32_t stamp;            // this call's mark on the entries above an edited leaf
+    const uint4* rec;
+    const int2* slot;
+    const HkLightRaw* leaf;
+    DLight* lights;
+    HkLightRaw* raw;
+    DLightNode* lnodes;
+    const int* parent;
+    const int* leaf_entry;
+    uint32_t* stamps;
+};
+
 // hk_scene_rebuild_bvh: the device builder's state (k_build_*, hk_build_kernels.h).  A SEGMENT is a range of the index array that becomes
 // an inner node: level L's segments, in breadth-first order, are nodes level_start[L] + 0, 1, ...; `large` >= 0 names the segment's
 // slot in the global bin storage (it is binned by many blocks), < 0: one block bins it in LDS.

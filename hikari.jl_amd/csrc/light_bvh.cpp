@@ -5,10 +5,12 @@
 // LightBounds / DirectionCone union (src/lights/light-bounds.jl:24-158), light_bounds per light
 // type (:231-295), _evaluate_cost (:242-259).  12 buckets, swap partition, bit trails by depth.
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <utility>
 
 #include "bvh_build.h"
+#include "hk_light_bounds.h"
 
 namespace hk {
 namespace {
@@ -164,22 +166,22 @@ int bucket(f3 clo, f3 chi, f3 c, int dim) {
     return (b < 0 ? 0 : (b > 11 ? 11 : b)) + 1;
 }
 
+LightBVHNodeH node_of(const LB& lb, uint32_t child, bool leaf) {
+    LightBVHNodeH n;
+    std::memset(&n, 0, sizeof n);
+    n.bmin[0] = lb.lo.x; n.bmin[1] = lb.lo.y; n.bmin[2] = lb.lo.z;
+    n.bmax[0] = lb.hi.x; n.bmax[1] = lb.hi.y; n.bmax[2] = lb.hi.z;
+    n.w[0] = lb.w.x; n.w[1] = lb.w.y; n.w[2] = lb.w.z;
+    n.phi = lb.phi;
+    n.cos_o = lb.cos_o;
+    n.cos_e = lb.cos_e;
+    n.bits = (lb.two_sided ? 1u : 0u) | (leaf ? 2u : 0u);
+    n.child1_or_light = child;
+    return n;
+}
 struct Rec {
     std::vector<std::pair<int, LB>>& L;
     LightBVH& out;
-    LightBVHNodeH node_of(const LB& lb, uint32_t child, bool leaf) {
-        LightBVHNodeH n;
-        std::memset(&n, 0, sizeof n);
-        n.bmin[0] = lb.lo.x; n.bmin[1] = lb.lo.y; n.bmin[2] = lb.lo.z;
-        n.bmax[0] = lb.hi.x; n.bmax[1] = lb.hi.y; n.bmax[2] = lb.hi.z;
-        n.w[0] = lb.w.x; n.w[1] = lb.w.y; n.w[2] = lb.w.z;
-        n.phi = lb.phi;
-        n.cos_o = lb.cos_o;
-        n.cos_e = lb.cos_e;
-        n.bits = (lb.two_sided ? 1u : 0u) | (leaf ? 2u : 0u);
-        n.child1_or_light = child;
-        return n;
-    }
     LB go(int start, int stop, uint32_t trail, int depth) {  // 1-based inclusive
         int count = stop - start + 1;
         if (count == 1) {
@@ -340,6 +342,97 @@ void derive_light_tables(const hk_light* lights, int n, LightBVH& bvh, LightTabl
     if (out.infinite.empty()) out.infinite.resize(1);
     out.num_bvh = bvh.num_bvh;
     out.num_infinite = (int)bvh.infinite.size();
+}
+
+// ---- the refit (hk_scene_refit_lights): leaves from bounds_of, inner nodes from hk_light_bounds.h, the topology as built ----
+int light_leaf(const hk_light& l, int light_1based, LightBVHNodeH& leaf) {
+    LB lb;
+    std::memset(&leaf, 0, sizeof leaf);
+    if (!bounds_of(l, lb)) return 0;
+    if (!(lb.phi > 0.0f)) return 1;   // build_light_bvh's test: such a light is bounded, and outside the tree
+    leaf = node_of(lb, (uint32_t)light_1based, true);
+    return 2;
+}
+
+// sibling_pair_order's walk once more, keeping what it forgets: where every host node went, who its parent is, how deep it lies
+void light_refit_layout(const LightBVH& bvh, LightRefitLayout& out) {
+    const size_t N = bvh.nodes.size();
+    out = LightRefitLayout{};
+    out.leaf_entry.assign(bvh.bit_trails.size(), -1);
+    out.level_start.assign(1, 0);
+    if (N == 0) return;
+    out.entry_of_host.assign(N, -1);
+    out.host_of_entry.assign(2, -1);
+    out.parent.assign(2, -1);
+    out.entry_of_host[0] = 0, out.host_of_entry[0] = 0;
+    struct Todo {
+        uint32_t host, entry;
+        int depth;
+    };
+    std::vector<Todo> todo{{0u, 0u, 0}};
+    std::vector<std::vector<int32_t>> levels;
+    for (size_t q = 0; q < todo.size(); ++q) {
+        const Todo t = todo[q];
+        const LightBVHNodeH& nd = bvh.nodes[t.host];
+        if (nd.bits & 2u) {
+            out.leaf_entry[nd.child1_or_light - 1] = (int32_t)t.entry;
+            continue;
+        }
+        if ((size_t)t.depth >= levels.size()) levels.resize((size_t)t.depth + 1);
+        levels[(size_t)t.depth].push_back((int32_t)t.entry);
+        const uint32_t h0 = t.host + 1, h1 = nd.child1_or_light - 1, base = (uint32_t)out.host_of_entry.size();
+        out.host_of_entry.push_back((int32_t)h0), out.host_of_entry.push_back((int32_t)h1);
+        out.parent.push_back((int32_t)t.entry), out.parent.push_back((int32_t)t.entry);
+        out.entry_of_host[h0] = (int32_t)base, out.entry_of_host[h1] = (int32_t)base + 1;
+        todo.push_back(Todo{h0, base, t.depth + 1});
+        todo.push_back(Todo{h1, base + 1, t.depth + 1});
+    }
+    out.n_entries = (int)out.host_of_entry.size();
+    for (const auto& lv : levels) {
+        out.level_entries.insert(out.level_entries.end(), lv.begin(), lv.end());
+        out.level_start.push_back((int32_t)out.level_entries.size());
+    }
+}
+
+namespace {
+HkLightRaw raw_of(const LightBVHNodeH& n) {
+    static_assert(sizeof(HkLightRaw) == sizeof(LightBVHNodeH) && sizeof(HkLightWalk) == sizeof(LightNodeRec), "hk_light_bounds.h restates the two node layouts");
+    static_assert(offsetof(HkLightRaw, phi) == offsetof(LightBVHNodeH, phi) && offsetof(HkLightRaw, child1_or_light) == offsetof(LightBVHNodeH, child1_or_light), "raw node layout");
+    static_assert(offsetof(HkLightWalk, r2) == offsetof(LightNodeRec, r2) && offsetof(HkLightWalk, sin_o) == offsetof(LightNodeRec, sin_o) && offsetof(HkLightWalk, child1_or_light) == offsetof(LightNodeRec, child1_or_light), "walked node layout");
+    HkLightRaw r;
+    std::memcpy(&r, &n, sizeof r);
+    return r;
+}
+}  // namespace
+
+// The host twin of the device refit: the arithmetic of hk_light_bounds.h over the same arrays in the same order.  bvh: the tree in
+// host order (its topology and trails are not touched), t: the device tables; both are rewritten on the paths from the edited leaves
+// to the root.  The caller has checked what hk_scene_refit_lights checks; a light outside the tree changes neither.
+void refit_light_bvh(LightBVH& bvh, LightTables& t, const LightRefitLayout& lay, int n, const int32_t* index, const hk_light* lights) {
+    if (lay.n_entries == 0) return;
+    std::vector<char> dirty((size_t)lay.n_entries, 0);
+    for (int j = 0; j < n; ++j) {
+        const int32_t e = lay.leaf_entry[(size_t)index[j]];
+        LightBVHNodeH leaf;
+        if (e < 0 || light_leaf(lights[j], index[j] + 1, leaf) != 2) continue;
+        bvh.nodes[(size_t)lay.host_of_entry[(size_t)e]] = leaf;
+        const HkLightWalk w = hk_lb_walk_record(raw_of(leaf), (uint32_t)(index[j] + 1));
+        std::memcpy(&t.nodes[(size_t)e], &w, sizeof w);
+        for (int32_t p = lay.parent[(size_t)e]; p >= 0; p = lay.parent[(size_t)p]) dirty[(size_t)p] = 1;
+    }
+    for (int d = (int)lay.level_start.size() - 2; d >= 0; --d)
+        for (int32_t k = lay.level_start[(size_t)d]; k < lay.level_start[(size_t)d + 1]; ++k) {
+            const int32_t e = lay.level_entries[(size_t)k];
+            if (!dirty[(size_t)e]) continue;
+            const uint32_t c = t.nodes[(size_t)e].child1_or_light;
+            const HkLightRaw u = hk_lb_union(raw_of(bvh.nodes[(size_t)lay.host_of_entry[c]]), raw_of(bvh.nodes[(size_t)lay.host_of_entry[c + 1]]));
+            LightBVHNodeH& h = bvh.nodes[(size_t)lay.host_of_entry[(size_t)e]];
+            const uint32_t host_child1 = h.child1_or_light;
+            std::memcpy(&h, &u, sizeof h);
+            h.child1_or_light = host_child1;
+            const HkLightWalk w = hk_lb_walk_record(u, c);
+            std::memcpy(&t.nodes[(size_t)e], &w, sizeof w);
+        }
 }
 
 // rgb_to_spectrum (spectral/rgb2spec.jl:85-167): host-side bake of constant colours

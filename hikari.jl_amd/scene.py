@@ -27,6 +27,16 @@ class SceneInstance:
         return "SceneInstance(mi_idx=%d, first_tri=%d, n_tris=%d)" % (self.mi_idx, self.first_tri, self.n_tris)
 
 
+def _move_lights_tree(move_lights):
+    """move_lights of set_transform / set_vertices -> the `tree` of update_lights: False / True keep their meaning (True rebuilds the
+    light BVH), "refit" refits it on the device."""
+    if isinstance(move_lights, str):
+        if move_lights != "refit":
+            raise ValueError("move_lights must be False, True or 'refit', got %r" % (move_lights,))
+        return "refit"
+    return "rebuild"
+
+
 def _affine_3x4(m4x4):
     """The 3x4 row-major affine part of a 4x4 transform; refuses what hk_scene_set_transform would refuse (ValueError)."""
     m = np.asarray(m4x4, dtype=np.float64)
@@ -176,19 +186,34 @@ class Scene:
         point formula, then _face_light_geometry as at push time) and sent with hk_scene_update_lights, one call per contiguous run
         of flat light indices; the light BVH is rebuilt.  A face whose moved edge cross product falls under the 1e-10 cut-off (a
         push would not have registered it) keeps its record with area = 0: zero power, so it leaves the tree, and comes back with
-        the next transform that gives it an area."""
+        the next transform that gives it an area.  move_lights="refit": the moved records go in ONE hk_scene_refit_lights call per
+        device scene and the light BVH is refit on the device (update_light's tree="refit"); a face that degenerates or comes back
+        would leave or enter the tree, which a refit refuses: ValueError before anything is moved — use True for such a move."""
         if not isinstance(instance, SceneInstance):
             raise TypeError("set_transform takes the SceneInstance push_instance returned")
         m34 = _affine_3x4(m4x4)
         if instance.n_tris < 1 or instance.first_tri < 0 or instance.first_tri + instance.n_tris > self.n_triangles():
             raise ValueError("instance %r is not a triangle range of this scene" % (instance,))
         moved = self._moved_area_lights(instance, m34) if move_lights else []
+        tree = _move_lights_tree(move_lights)
+        self._check_refit_moves(moved, tree)                # before anything changes: geometry and lights move together or not at all
         self._transforms[(instance.first_tri, instance.n_tris)] = m34
         from . import _lib
         for h in (getattr(self, "_device", None) or {}).values():
             _lib.check(_lib.lib().hk_scene_set_transform(h, instance.first_tri, instance.n_tris, m34.ctypes.data_as(A.PF)), "hk_scene_set_transform")
         if moved:
-            self._replace_lights(moved)
+            self._replace_lights(moved, tree)
+
+    def _check_refit_moves(self, moved, tree):
+        """A refit keeps every light's membership in the light tree; of a moved face light only its area decides it (Le and scale are
+        kept).  ValueError for a face that degenerates (area -> 0) or comes back, which hk_scene_refit_lights would refuse AFTER the
+        geometry had moved."""
+        if tree != "refit":
+            return
+        for index, light in moved:
+            if (light.area > 0) != (self.lights[index].area > 0):
+                raise ValueError("move_lights='refit': the area light of light %d would %s the light tree (its face %s); use move_lights=True for this move"
+                                 % (index, "leave" if self.lights[index].area > 0 else "enter", "degenerates" if self.lights[index].area > 0 else "gets an area again"))
 
     def _mesh_index(self, instance):
         """Position in self._meshes of the mesh `instance` was pushed as."""
@@ -223,7 +248,8 @@ class Scene:
         move_lights=False (the default): area lights stay as they are, as with set_transform (Q18).  move_lights=True: every face
         light of the instance is recomputed from the new vertices under the instance's current transform (_face_light_geometry, a
         degenerate face keeping its record with area = 0, as set_transform(move_lights=True) does) and, with `uvs`, carries the new
-        uvs; its Le is kept (a textured emission is not sampled again).  Which faces emit does not change.
+        uvs; its Le is kept (a textured emission is not sampled again).  Which faces emit does not change.  move_lights="refit": as
+        set_transform's — one hk_scene_refit_lights call per device scene, the light BVH refit on the device.
 
         ValueError for what the library would refuse: a wrong shape, a non-finite position, normals / uvs for a mesh pushed without."""
         if not isinstance(instance, SceneInstance):
@@ -254,9 +280,11 @@ class Scene:
                 raise ValueError("set_vertices: uvs for a mesh pushed without uvs")
             U = take(uvs, (n, 3, 2), "uvs")
         moved = []
+        tree = _move_lights_tree(move_lights)
         if move_lights:
             m34 = self._transforms.get((instance.first_tri, n), np.eye(3, 4, dtype=f32))
             moved = self._moved_area_lights(instance, m34, P, U)
+        self._check_refit_moves(moved, tree)                # before anything changes
         self._meshes[k] = (G.Mesh(P.copy(), mesh.normals if N is None else N.copy(), mesh.uvs if U is None else U.copy()), metas)
         a, e = instance.first_tri, instance.first_tri + n
         if self._desc is not None:              # the arrays the kept description points into, rewritten in place
@@ -274,7 +302,7 @@ class Scene:
         for h in (getattr(self, "_device", None) or {}).values():
             _lib.check(_lib.lib().hk_scene_set_vertices(h, a, n, ptr(P), ptr(N), None, ptr(U)), "hk_scene_set_vertices")
         if moved:
-            self._replace_lights(moved)
+            self._replace_lights(moved, tree)
 
     def bvh_cost(self, ctx):
         """(now, created) of hk_scene_bvh_cost for this scene on `ctx`: the cost of the BVH as the device holds it after the refits
@@ -329,15 +357,20 @@ class Scene:
                 return i
         raise ValueError("light %d is not in the flat order" % index)
 
-    def _replace_lights(self, pairs):
+    def _replace_lights(self, pairs, tree="rebuild"):
         """pairs: [(index into self.lights, new light of the same class)].  Rewrites self.lights, the kept description and every
-        device scene — contiguous runs of FLAT indices (flat_lights() order, what hk_scene_desc::lights holds) in one call each."""
+        device scene.  tree="rebuild": contiguous runs of FLAT indices (flat_lights() order, what hk_scene_desc::lights holds) in one
+        hk_scene_update_lights call each.  tree="refit": the whole set in ONE hk_scene_refit_lights call per device scene."""
+        if tree not in ("rebuild", "refit"):
+            raise ValueError("tree must be 'rebuild' or 'refit', got %r" % (tree,))
         for index, light in pairs:
             if not 0 <= index < len(self.lights):
                 raise IndexError("light index %d out of range" % index)
             if type(light) is not type(self.lights[index]):
                 raise TypeError("update_light: %s cannot replace %s (the class must match)" % (type(light).__name__, type(self.lights[index]).__name__))
         flat = [self._flat_index(index) for index, _ in pairs]
+        if tree == "refit" and len(set(flat)) != len(flat):
+            raise ValueError("update_lights(tree='refit'): a light is given twice")
         recs = None
         if self._desc is not None:      # (before the first sync there is no description: the next one flattens the new lights)
             n_tex, n_env = len(self.textures), len(self._envmaps)
@@ -348,12 +381,20 @@ class Scene:
                 del self.textures[n_tex:], self._envmaps[n_env:]
             if added:
                 raise ValueError("update_light: the new light references a texture or an environment map that is not in the scene")
+        from . import _lib
+        if tree == "refit" and recs is not None and pairs:
+            # the device scenes first: a refit the library refuses (a light entering or leaving the tree) leaves everything as it was
+            idx = (C.c_int32 * len(flat))(*flat)
+            arr = (A.hk_light * len(recs))(*recs)
+            for h in (getattr(self, "_device", None) or {}).values():
+                _lib.check(_lib.lib().hk_scene_refit_lights(h, len(flat), idx, arr), "hk_scene_refit_lights")
+            for k, rec in zip(flat, recs):
+                self._desc.lights[k] = rec
         for index, light in pairs:
             self.lights[index] = light
-        if recs is None:
+        if recs is None or tree == "refit":
             return
         order = sorted(range(len(flat)), key=lambda k: flat[k])
-        from . import _lib
         k = 0
         while k < len(order):
             e = k + 1
@@ -366,12 +407,22 @@ class Scene:
                 _lib.check(_lib.lib().hk_scene_update_lights(h, flat[order[k]], e - k, run), "hk_scene_update_lights")
             k = e
 
-    def update_light(self, index, light):
+    def update_light(self, index, light, tree="rebuild"):
         """The light self.lights[index] (0-based position in push order: push_light's return value minus one) is replaced by
         `light`, an object of the same class: dim a lamp, move a point light, turn the sun, re-colour an emitter (a
         DiffuseAreaLight: its Le, scale, two_sided, geometry).  The description holds the lights in flat_lights() order; the index
-        is mapped through it."""
-        self._replace_lights([(index, light)])
+        is mapped through it.
+
+        tree="rebuild" (the default): every device scene rebuilds its light BVH on the host (hk_scene_update_lights) and is, bit for
+        bit, the scene a fresh hk_scene_create makes of the edited description.  tree="refit": the tree keeps its topology and is
+        refit on the device (hk_scene_refit_lights) — interactive on many lights, the same expected image with another pmf; a light
+        may not enter or leave the tree (a power going to or from zero), which the library refuses with nothing changed.  The kept
+        description is rewritten either way, so a device scene created LATER from it has the fresh tree."""
+        self._replace_lights([(index, light)], tree)
+
+    def update_lights(self, pairs, tree="rebuild"):
+        """update_light for a set: pairs = [(index, light)].  tree="refit" sends the whole set in one call per device scene."""
+        self._replace_lights(list(pairs), tree)
 
     def update_envmap(self, env_map, data=None, rotation=None):
         """New texels (same size, [height, width, 3 or 4]) and / or a new 3x3 rotation for an EnvironmentMap of this scene, in the

@@ -443,6 +443,32 @@ int32_t hk_scene_update_lights(hk_scene* scene, int32_t first, int32_t n, const 
 int32_t hk_scene_update_envmap(hk_scene* scene, int32_t idx, const float* data, const float* rotation);
 int32_t hk_scene_update_medium(hk_scene* scene, int32_t idx, const hk_medium* medium);
 
+/* hk_scene_refit_lights: new records for a SET of lights, and the light BVH REFIT on the device instead of rebuilt on the host — what
+ * hk_scene_set_transform is to the geometry, with hk_scene_update_lights as the rebuild.  index[0 .. n-1] are distinct 0-based indices
+ * into hk_scene_desc::lights in any order, lights[j] replaces light index[j].  The topology of the tree stays: bit trails, node
+ * count, the two light counts and the infinite list are unchanged.  Leaves: the bounds of an edited light are the builder's own,
+ * computed on the host, so a refit leaf is bit for bit the leaf a fresh scene has for that light.  Inner nodes: every node on a path
+ * from an edited leaf to the root becomes the union of its two children (box, phi = the binary32 sum, cos_e = the min, two_sided = the
+ * or, the cone by the reference's DirectionCone union with two statements added: the rotation axis is made perpendicular to the first
+ * child's axis again, because a kept topology pairs lights of nearly opposite axes, for which the cross product is rounding noise, and
+ * the cosine of the union's angle is stepped one to two ulps towards -1, so that the cone errs to the outside), deepest first, and the
+ * record the sampler walks is derived from it; every other node keeps its bits.  The union's asin / acos / sin / cos are binary32 routines of the library (csrc/hk_light_bounds.h: + - * / sqrt
+ * only, the same bits on the device and on the host), NOT libm's: with those and the two statements above, the cone of a refit inner
+ * node differs from a built one in its last places, also where no record changed.  Light sampling and its MIS pdf read the same tree, so a refit scene renders the same expected
+ * image with another pmf — it is NOT bit for bit the scene hk_scene_create builds from the edited description, and a tree refit
+ * after large moves selects lights less well than a rebuilt one.  hk_scene_update_lights (any record, also an unchanged one)
+ * rebuilds from the current records and gives the fresh scene again.
+ * Ordering as for every edit: noted calls render first, the work is enqueued on the context's stream, the call does not wait.  The
+ * upload, through pinned memory of the scene, is proportional to the edit: n baked records and one 64-byte leaf per edited light of
+ * the tree.  A scene's FIRST refit (and the first after a rebuild) also uploads the tree as built, its parent links and level lists.
+ * After a refit hk_scene_light_bvh_copy reads the tree back from the device and waits for it.
+ * Refused, each HK_ERR_INVALID with the scene untouched: a null pointer, n < 1 or n above the light count, an index out of range or
+ * given twice, what hk_scene_update_lights refuses of a record (another kind, envmap or Le.tex out of range), a non-finite position
+ * (point, spot), vertex, normal or area (area light) or bounds, and a light whose membership in the tree would change — bounded lights
+ * (point, spot, area) of positive power are in the tree, infinite kinds and lights of zero power are not; an edit that moves a light
+ * into or out of the tree goes through hk_scene_update_lights, and the error text says so. */
+int32_t hk_scene_refit_lights(hk_scene* scene, int32_t n, const int32_t* index, const hk_light* lights);
+
 /* hk_scene_update_medium_dense: NanoVDB medium `idx` becomes the tree of a dense density field, and the tree is built ON THE DEVICE.
  * Of *medium the call reads kind, sigma_a, sigma_s, Le, g, bounds_min, bounds_max and majorant_res (which must be unchanged) — and, like
  * hk_scene_update_medium, the two transforms; every NanoVDB field (nvdb_bytes, nvdb_size, offsets, counts, inv_mat, vec, index_bbox_*),
@@ -630,6 +656,13 @@ int32_t hk_test_uplift(hk_ctx* ctx, int32_t mode, int32_t n, const float* rgb, c
 /* light-BVH: sample (light_idx_1based, pmf) and pmf of a given light for n shading points */
 int32_t hk_test_light_bvh(hk_ctx* ctx, hk_scene* scene, int32_t n, const float* p3, const float* n3, const float* u,
                           int32_t* out_light, float* out_pmf, const int32_t* query_light, float* out_query_pmf);
+/* the host twin of hk_scene_refit_lights, no device involved: the tree built from lights[0 .. n_lights-1], then n_calls refits in turn
+   (call k takes the next call_n[k] entries of index / records).  Out: the tree as hk_scene_light_bvh_copy hands it out, and the table
+   the sampler walks (16 words per entry, 2 n_lights entries, device order).  HK_ERR_INVALID for an edit the entry point refuses. */
+int32_t hk_test_light_refit_host(const hk_light* lights, int32_t n_lights, int32_t n_calls, const int32_t* call_n, const int32_t* index,
+                                 const hk_light* records, int32_t* n_nodes, float* nodes_out, uint32_t* bit_trails, uint32_t* table_out);
+/* that table as the device holds it now: 16 words per entry, 2 max(n_lights, 1) entries (waits for the context's stream) */
+int32_t hk_test_light_table_copy(hk_scene* scene, uint32_t* table_out);
 /* ---------------------------------------------------------------------------------------------
  * postprocess!(film; exposure, tonemap, gamma, white_point, sensor, background)  (src/postprocess.jl:293-357).
  * Non-destructive: reads the film's current rgb/weight, writes tonemapped RGB to `dst` (host, Julia [h,w] RGB{Float32}
@@ -737,6 +770,7 @@ int32_t hk_test_trace_lean(hk_ctx* ctx, hk_scene* scene, int32_t anyhit, int32_t
 
 /* introspection used by tests/bench */
 int32_t hk_scene_bvh_info(hk_scene* scene, int32_t* n_nodes, int32_t* n_leaf_tris, int32_t* max_depth);
+/* (after hk_scene_refit_lights: the refit tree, read back from the device — the call waits for the context's stream) */
 int32_t hk_scene_light_bvh_copy(hk_scene* scene, int32_t* n_nodes, float* nodes_out /* 16 floats per node */,
                                 uint32_t* bit_trails /* n_lights */);
 /* The cost of the scene's BVH as the device holds it (cost_now) and as hk_scene_create built it (cost_created): the sum over the inner

@@ -654,13 +654,28 @@ end
 # Lights, environment maps and media in place (hk_scene_update_lights / hk_scene_update_envmap / hk_scene_update_medium): the scene on the device is edited, not rebuilt
 # ---------------------------------------------------------------------------------------------------------------------------
 """
-    update_light!(vp, flat_index, light; envmap_index = 0)
+    update_light!(vp, flat_index, light; envmap_index = 0, tree = :rebuild)
 
 Replaces light `flat_index` (0-based, in the `flat_to_light_index` order `flatten_scene` uploads) of the scene `vp` holds on its devices
-by `light`, which must be of the same type.  The library rebuilds the light BVH; films are not cleared.  An `EnvironmentLight` keeps
-pointing at map `envmap_index` of the scene; a textured `Le` cannot be introduced by an update.
+by `light`, which must be of the same type.  `tree = :rebuild`: the library rebuilds the light BVH on the host (the scene a fresh upload
+would give, bit for bit).  `tree = :refit`: the tree keeps its topology and is refit on the device (`refit_lights!`).  Films are not
+cleared.  An `EnvironmentLight` keeps pointing at map `envmap_index` of the scene; a textured `Le` cannot be introduced by an update.
 """
-function update_light!(vp::MI355XVolPath, flat_index::Integer, light; envmap_index::Integer = 0)
+function update_light!(vp::MI355XVolPath, flat_index::Integer, light; envmap_index::Integer = 0, tree::Symbol = :rebuild)
+    tree in (:rebuild, :refit) || error("HikariMI355X: update_light!: tree must be :rebuild or :refit")
+    if tree === :refit
+        return refit_lights!(vp, [flat_index], [light]; envmap_index = envmap_index)
+    end
+    rec = edited_light_record(light, envmap_index)
+    for d in vp.devs
+        d.scene == C_NULL && continue
+        check(ccall((:hk_scene_update_lights, LIB), Int32, (Ptr{Cvoid}, Int32, Int32, Ref{HkLight}), d.scene, Int32(flat_index), Int32(1), rec), "hk_scene_update_lights")
+    end
+    nothing
+end
+
+# the record of a light that replaces one of the scene: no texture may come with it
+function edited_light_record(light, envmap_index::Integer)
     fl = Flattener(nothing, HkTexture[], Dict{UInt,Int32}(), HkPlSpectrum[], HkEnvmap[], Any[])
     rec = if light isa Hikari.EnvironmentLight
         HkLight(HK_LIGHT_ENVIRONMENT, HK_SPEC_RGB, rgba(light.scale), Z3, 0f0, 1f0, Z3, Z3, Z16, Z16, 0f0, 0f0, Z9, Z3, 0f0, Z6, NO_RGBA, 0, Int32(envmap_index))
@@ -668,9 +683,25 @@ function update_light!(vp::MI355XVolPath, flat_index::Integer, light; envmap_ind
         light_record(fl, light)
     end
     isempty(fl.textures) || error("HikariMI355X: update_light! cannot add a texture to the scene")
+    rec
+end
+
+"""
+    refit_lights!(vp, flat_indices, lights; envmap_index = 0)
+
+New records for a set of lights (distinct 0-based flat indices, any order) in ONE `hk_scene_refit_lights` call per device: the light BVH
+keeps its topology and is refit on the device — the nodes above the edited leaves are recomputed, everything else keeps its bits.  The
+expected image is that of a rebuilt tree, the pmf is not; a light may not enter or leave the tree (a power going to or from zero): the
+library refuses such an edit and `update_light!` with `tree = :rebuild` takes it.
+"""
+function refit_lights!(vp::MI355XVolPath, flat_indices, lights; envmap_index::Integer = 0)
+    length(flat_indices) == length(lights) || error("HikariMI355X: refit_lights!: as many lights as indices")
+    idx = Int32[Int32(i) for i in flat_indices]
+    recs = HkLight[edited_light_record(l, envmap_index) for l in lights]
+    isempty(idx) && return nothing
     for d in vp.devs
         d.scene == C_NULL && continue
-        check(ccall((:hk_scene_update_lights, LIB), Int32, (Ptr{Cvoid}, Int32, Int32, Ref{HkLight}), d.scene, Int32(flat_index), Int32(1), rec), "hk_scene_update_lights")
+        check(ccall((:hk_scene_refit_lights, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{HkLight}), d.scene, Int32(length(idx)), idx, recs), "hk_scene_refit_lights")
     end
     nothing
 end
